@@ -27,6 +27,18 @@ Modes:
                  region, same bracketing) and job-to-Running latency
                  comes from the job's condition timestamps.
 
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print the result line. --full additionally runs the
+secondary measurements (there are none at present; the flag is accepted
+so callers that want everything can always pass it).
+
+--dump-outputs DIR writes what the last timed step computed (rank 0):
+  loss.npy           float32 [1]   the loss train_step returned
+  params_sample.npy  float32 [n]   the updated parameters, a fixed seeded
+                                   sample of every flat bucket
+Inputs and initial weights are seeded, so two builds run with the same
+arguments can be compared output for output.
+
 Synthetic data (no network for datasets), random-init weights, bf16.
 """
 from __future__ import annotations
@@ -71,7 +83,16 @@ def parse_args(argv=None):
                     help="cpu is for harness self-tests only (gloo)")
     ap.add_argument("--timeout", type=float, default=1800.0,
                     help="via-manager: max seconds to wait for the job")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (none at "
+                         "present: a plain run is the headline figure only)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write the last step's "
+                         "outputs to DIR/<name>.npy (float32)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.via_manager:
+        ap.error("--dump-outputs is not supported with --via-manager")
+    return args
 
 
 def _resolve_hip_graph(args, world: int) -> bool:
@@ -120,6 +141,33 @@ def emit(args, *, value, elapsed, n_gpus, loss, extra_config=None):
         },
     }
     print(json.dumps(out), flush=True)
+
+
+DUMP_SEED = 20240607
+DUMP_PER_BUCKET = 65536  # sampled elements per flat bucket (<= 64 MB total)
+
+
+def dump_outputs(out_dir, trainer, loss):
+    """Write what the last timed train_step produced: its return value
+    (the loss) and its effect (the updated parameters; a fixed, seeded
+    sample of each flat bucket so an 8B model stays a few MB)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().reshape(1).cpu().numpy())
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(DUMP_SEED)
+    parts = []
+    for b in trainer.fb.buckets:
+        flat = b.flat_param.detach()
+        if b.numel > DUMP_PER_BUCKET:
+            idx = torch.randint(0, b.numel, (DUMP_PER_BUCKET,), generator=gen)
+            flat = flat.index_select(0, idx.to(flat.device))
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"),
+            torch.cat(parts).numpy())
 
 
 def run_direct(args):
@@ -187,6 +235,9 @@ def run_direct(args):
                          device=ctx.device if args.device == "cuda" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+
+    if args.dump_outputs and ctx.is_main:
+        dump_outputs(args.dump_outputs, trainer, loss)
 
     tokens_total = args.micro_batch * args.seq_len * n_gpus * args.steps
     if ctx.is_main:

@@ -66,6 +66,48 @@ def test_bench_refuses_world_size_mismatch():
     assert "{" not in r.stdout  # no JSON metric line emitted
 
 
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's loss and parameter
+    sample as float32 .npy; the same arguments give the same inputs, so
+    two runs agree (CPU fp32 is deterministic). The second run passes
+    --full, which must be accepted and leave the headline line as is."""
+    import numpy as np
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = subprocess.run(
+            [sys.executable, BENCH, "--gpus", "1", "--dump-outputs", str(d)]
+            + extra + TINY,
+            capture_output=True, text=True, timeout=180, env=_clean_env(),
+            cwd=REPO)
+        assert r.returncode == 0, f"stdout={r.stdout}\nstderr={r.stderr}"
+        out = _last_json_line(r.stdout)
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        assert sorted(p.name for p in d.iterdir()) == \
+            ["loss.npy", "params_sample.npy"]
+        loss = np.load(d / "loss.npy")
+        params = np.load(d / "params_sample.npy")
+        assert loss.dtype == np.float32 and loss.shape == (1,)
+        assert params.dtype == np.float32 and params.ndim == 1
+        assert params.size > 0 and np.isfinite(params).all()
+        assert loss[0] == np.float32(out["config"]["loss"])
+        assert loss.nbytes + params.nbytes <= 64 * 2**20
+        dumps.append((loss, params))
+    assert np.array_equal(dumps[0][0], dumps[1][0])
+    assert np.array_equal(dumps[0][1], dumps[1][1])
+
+
+def test_bench_dump_outputs_refused_via_manager(tmp_path):
+    r = subprocess.run(
+        [sys.executable, BENCH, "--gpus", "1", "--via-manager",
+         "--dump-outputs", str(tmp_path / "d")] + TINY,
+        capture_output=True, text=True, timeout=180, env=_clean_env(),
+        cwd=REPO)
+    assert r.returncode == 2
+    assert "--dump-outputs" in r.stderr
+    assert not (tmp_path / "d").exists()
+
+
 @pytest.mark.parametrize("n", [1, 2])
 def test_bench_via_manager(n):
     """The headline path: gang-scheduled TorchJob through the manager,

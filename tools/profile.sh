@@ -1,15 +1,16 @@
 #!/bin/bash
-# rocprofv3 recipes for this repo (run on an MI355X box via gpurun).
+# rocprofv3 recipes for this repo (run on an MI355X box).
 # Counter collection must NOT be combined with sys/runtime/hip trace
 # domains (suspected node-crasher on this pool) — keep the two modes
 # below separate.
 set -e
+REPO=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 export TMPDIR=/tmp
 cd /tmp
-OUT=${OUT:-/root/repo/gpurun_out/prof_$(date +%s 2>/dev/null || echo run)}
+OUT=${OUT:-$REPO/prof_out/prof_$(date +%s 2>/dev/null || echo run)}
 MODE=${1:-stats}
 shift || true
-CMD=${@:-"python /root/repo/bench.py --steps 2 --warmup 1"}
+CMD=${@:-"python $REPO/bench.py --steps 2 --warmup 1"}
 
 case "$MODE" in
   stats)   # per-kernel timing breakdown -> <OUT>/**/*_results.db (rocpd)
@@ -20,4 +21,4 @@ case "$MODE" in
   *) echo "usage: profile.sh [stats|pmc] [command...]"; exit 2 ;;
 esac
 echo "wrote $OUT  (query top_kernels / counters_collection in the .db;"
-echo " commit summaries to /root/repo/profiles/)"
+echo " commit summaries to $REPO/profiles/)"
