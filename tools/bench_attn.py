@@ -2,8 +2,10 @@
 """Attention kernel microbenchmark (dev tool, not the driver contract).
 
 Measures fwd / bwd wall time and effective TFLOP/s of the gfx950 flash
-attention at the flagship shape, A/B against torch SDPA. Within-process
-interleaved rounds (guide §5.4 rule 24).
+attention at the flagship shape, A/B against torch SDPA. The backward is
+timed both ways, fused dK+dV (default) and split dV / dK, side by side.
+Within-process interleaved rounds (guide §5.4 rule 24). The flagship
+per-layer shape is --B 8; record runs at both --B 2 and --B 8.
 """
 import argparse
 import os
@@ -42,6 +44,8 @@ def main():
     ap.add_argument("--D", type=int, default=128)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--no-sdpa", action="store_true",
+                    help="skip the torch SDPA columns (saves time at B=8)")
     args = ap.parse_args()
     from torch_on_k8s_amd import ops
 
@@ -67,8 +71,11 @@ def main():
 
     o_, lse_ = hip_fwd()
 
-    def hip_bwd():
-        return ops._C.attn_bwd(q, k, v, o_, lse_, do, True)
+    def hip_bwd():      # fused dK+dV kernel (the default path)
+        return ops._C.attn_bwd(q, k, v, o_, lse_, do, True, False)
+
+    def hip_bwd_split():   # older split dV / dK kernels
+        return ops._C.attn_bwd(q, k, v, o_, lse_, do, True, True)
 
     qs = qt.detach().requires_grad_(True)
     ks = kt.detach().requires_grad_(True)
@@ -87,10 +94,20 @@ def main():
     for r in range(args.rounds):
         th_f = time_fn(hip_fwd, args.iters)
         th_b = time_fn(hip_bwd, args.iters)
+        th_bs = time_fn(hip_bwd_split, args.iters)
+        if args.no_sdpa:
+            print(f"[round {r}] hip fwd {th_f*1e3:7.2f} ms "
+                  f"{ffw/th_f/1e12:7.1f} TF"
+                  f" | hip bwd fused {th_b*1e3:7.2f} ms "
+                  f"{fbw/th_b/1e12:7.1f} TF"
+                  f" | hip bwd split {th_bs*1e3:7.2f} ms "
+                  f"{fbw/th_bs/1e12:7.1f} TF", flush=True)
+            continue
         ts_f = time_fn(sdpa_fwd, args.iters)
         ts_fb = time_fn(sdpa_fwdbwd, args.iters)
         print(f"[round {r}] hip fwd {th_f*1e3:7.2f} ms {ffw/th_f/1e12:7.1f} TF"
-              f" | hip bwd {th_b*1e3:7.2f} ms {fbw/th_b/1e12:7.1f} TF"
+              f" | hip bwd fused {th_b*1e3:7.2f} ms {fbw/th_b/1e12:7.1f} TF"
+              f" | hip bwd split {th_bs*1e3:7.2f} ms {fbw/th_bs/1e12:7.1f} TF"
               f" | sdpa fwd {ts_f*1e3:7.2f} ms {ffw/ts_f/1e12:7.1f} TF"
               f" | sdpa f+b {ts_fb*1e3:7.2f} ms "
               f"{(ffw+fbw)/ts_fb/1e12:7.1f} TF", flush=True)

@@ -21,15 +21,18 @@
 //    bit 7 swaps row parity in-tile for 128-B rows).
 //  * async-stage prefetch (T14), s_setprio around MFMA clusters (T5),
 //    defer-max online softmax (T13), interior tiles skip masking.
-//  * Backward: flash recompute scheme in three kernels - dV and dK split
-//    (a combined kernel needs 472 regs = 1 wave/SIMD and measured
-//    slower; split keeps 2 waves/SIMD), dQ over q tiles, plus a
-//    Dsum = rowsum(dO*O) preprocess. All kernels: 0 scratch spill.
+//  * Backward: flash recompute scheme in a Dsum = rowsum(dO*O) preprocess,
+//    one fused dK+dV kernel (64 keys per wave, 1 wave/SIMD, dK^T and dV^T
+//    in 256 accumulator registers, row constants as the accumulators'
+//    start values) and a deterministic dQ kernel over q tiles. The older
+//    split dV / dK pair (2 waves/SIMD, S recomputed in each) stays behind
+//    tok_attn_bwd's `split` selector for A/B timing. All kernels: 0
+//    scratch spill.
 //
 // Measured (B=2 S=4096 Hq=32 Hkv=8 D=128 causal, random data): fwd
-// 358-371 TF (parity with torch's aotriton flash), bwd 204-206 TF incl.
-// the three operand transposes (r2: uniform-flag interior fast path —
-// the bwd kernels are VALU-overhead-bound, profiles/pmc_attention_r2.csv).
+// 358-371 TF (parity with torch's aotriton flash); bwd incl. the three
+// operand transposes 292-294 TF fused, 212-214 TF with the split pair
+// (profiles/attn_dkdv.log).
 #include "common.h"
 
 namespace {
@@ -384,43 +387,92 @@ __global__ __launch_bounds__(NTHREADS) void attn_fwd_kernel_v3(
 // ========================================================================
 // Backward preprocess: Dsum[b,h,m] = sum_d dO*O (fp32)
 // ========================================================================
+// grid (ceil(S/PRE_ROWS), Hq, B), 256 threads. A group of D/8 lanes
+// covers one row with one uint4 each of dO and O (a 2*D-byte contiguous
+// read per row) and reduces with xor-shuffles inside the group; the
+// earlier one-thread-per-row form put neighbouring lanes 2*D bytes apart
+// and ran at 0.9 TB/s. A wave walks 16 consecutive s of one head, so its
+// 16 Dsum values leave as one contiguous 64-byte store. It also writes
+// the fused dK+dV kernel's accumulator start values (rc, see there).
+constexpr int PRE_ROWS = 64;   // s rows per block (16 per wave)
+
 template <int D>
-__global__ void attn_bwd_pre_kernel(const bf16_t* __restrict__ dout,
-                                    const bf16_t* __restrict__ o,
-                                    float* __restrict__ dsum, long rows,
-                                    int Hq, int S) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < rows;
-       i += (long)gridDim.x * blockDim.x) {
-    const bf16_t* dp = dout + i * D;
-    const bf16_t* opr = o + i * D;
-    float acc = 0.f;
-#pragma unroll 4
-    for (int cv = 0; cv < D / 8; ++cv) {
-      uint4 a = *(const uint4*)(dp + cv * 8);
-      uint4 b = *(const uint4*)(opr + cv * 8);
-      const uint16_t* ah = (const uint16_t*)&a;
-      const uint16_t* bh = (const uint16_t*)&b;
+__global__ __launch_bounds__(256) void attn_bwd_pre_kernel(
+    const bf16_t* __restrict__ dout, const bf16_t* __restrict__ o,
+    const float* __restrict__ lse, float* __restrict__ dsum,
+    float* __restrict__ rc, int Hq, int S, int S_pad, float sqrt_d) {
+  constexpr int GL = D / 8;        // lanes per row
+  constexpr int RPI = WAVE / GL;   // rows per wave per pass
+  constexpr int NP = 16 / RPI;     // passes per wave
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int grp = lane / GL, gl = lane % GL;
+  const int h = blockIdx.y;
+  const long b = blockIdx.z;
+  const int s0 = blockIdx.x * PRE_ROWS + wid * 16;
+  const long tok = (long)Hq * D;
+  const bf16_t* dp = dout + (b * S) * tok + (long)h * D + gl * 8;
+  const bf16_t* op = o + (b * S) * tok + (long)h * D + gl * 8;
+
+  uint4 av[NP], bv[NP];
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
-        acc = fmaf(bfbits2f(ah[j]), bfbits2f(bh[j]), acc);
+  for (int p = 0; p < NP; ++p) {
+    const int s = s0 + p * RPI + grp;
+    av[p] = bv[p] = uint4{0, 0, 0, 0};
+    if (s < S) {
+      av[p] = *(const uint4*)(dp + (long)s * tok);
+      bv[p] = *(const uint4*)(op + (long)s * tok);
     }
-    const long tok = i / Hq;
-    const long h = i - tok * Hq;
-    const long b_ = tok / S;
-    const long s_ = tok - b_ * S;
-    dsum[(b_ * Hq + h) * S + s_] = acc;
+  }
+  // lane i (< 16) of the wave ends up holding row s0+i
+  float mine = 0.f;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const uint16_t* ah = (const uint16_t*)&av[p];
+    const uint16_t* bh = (const uint16_t*)&bv[p];
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      acc = fmaf(bfbits2f(ah[j]), bfbits2f(bh[j]), acc);
+#pragma unroll
+    for (int off = GL / 2; off > 0; off >>= 1)
+      acc += __shfl_xor(acc, off, WAVE);
+    // row p*RPI + g sits in every lane of group g; collect it in lane
+    // (p*RPI + g) with one gather per pass
+#pragma unroll
+    for (int g = 0; g < RPI; ++g) {
+      const float vg = __shfl(acc, g * GL, WAVE);
+      if (lane == p * RPI + g) mine = vg;
+    }
+  }
+  if (lane < 16) {
+    const int s = s0 + lane;
+    if (s < S) dsum[(b * Hq + h) * S + s] = mine;
+    // start values of the fused dK+dV kernel's S and dP accumulators,
+    // [B,Hq,2,S_pad]: -lse*sqrt(D) (or -1e30: p == 0 exactly, for padded
+    // and lse == -inf rows) and -Dsum (0 for padded rows)
+    if (s < S_pad) {
+      float* r = rc + (b * Hq + h) * 2 * S_pad;
+      const float l = (s < S) ? lse[(b * Hq + h) * S + s] : NEG_INF;
+      r[s] = (l == NEG_INF) ? -1e30f : -l * sqrt_d;
+      r[S_pad + s] = (s < S) ? -mine : 0.f;
+    }
   }
 }
 
 // ========================================================================
-// Backward dV / dK v3: two kernels, grid (ceil(S/256), Hkv, B), 8 waves,
-// wave = 32 kv rows. Splitting dV and dK keeps each kernel at 2
-// waves/SIMD (a combined kernel needs dk+dv accumulators = 128 regs and
-// drops to 1 wave/SIMD, which measured SLOWER than the 16x16 v2 —
-// occupancy beats the saved recompute here). Swapped-operand structure
-// as the forward: K (and V in the dK kernel) live in registers as MFMA
-// B-operands; P^T / dS^T stay in-register and are repacked with
-// cvt_pk+permlane32_swap.
+// Backward dV / dK v3, SPLIT form: two kernels, grid (ceil(S/256), Hkv,
+// B), 8 waves, wave = 32 kv rows. Splitting dV and dK keeps each kernel
+// at 2 waves/SIMD; a combined kernel at 32 keys/wave needs dk+dv
+// accumulators = 128 regs, drops to 1 wave/SIMD with nothing to fill the
+// MFMA latency, and measured SLOWER than the 16x16 v2. The 64-keys-per-
+// wave combined kernel (attn_bwd_dkdv_kernel below) is the case that
+// conclusion left out: it accepts 1 wave/SIMD and gets its latency hiding
+// from two independent 32-key chains per wave. The split pair stays
+// selectable (tok_attn_bwd's `split` argument) so both can be timed in
+// one process. Swapped-operand structure as the forward: K lives in
+// registers as the MFMA B-operand; P^T / dS^T stay in-register and are
+// repacked with cvt_pk+permlane32_swap.
 // ========================================================================
 DEVINL void repack_pa(const f32x16& pt, bf16x8v& pa0, bf16x8v& pa1) {
   union { uint32_t w[4]; bf16x8v f; } f0, f1;
@@ -438,12 +490,8 @@ DEVINL void repack_pa(const f32x16& pt, bf16x8v& pa0, bf16x8v& pa1) {
   pa1 = f1.f;
 }
 
-// NWT (waves per block) A/B: 8 = one block/CU (lockstep phases);
-// 4 = TWO resident blocks/CU whose barrier phases drift, so each SIMD
-// hosts one wave of each block and staging overlaps the partner
-// block's MFMA segments (guide's compute/load wave-pair regime).
-template <int D, bool CAUSAL, int NWT = NW>
-__global__ __launch_bounds__(NWT * WAVE) void attn_bwd_dv_kernel(
+template <int D, bool CAUSAL>
+__global__ __launch_bounds__(NTHREADS) void attn_bwd_dv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ dot_t, const bf16_t* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ dsum,
@@ -451,8 +499,8 @@ __global__ __launch_bounds__(NWT * WAVE) void attn_bwd_dv_kernel(
     float scale) {
   constexpr int QC = D / 16;
   constexpr int DT = D / 32;
-  constexpr int NTH = NWT * WAVE;
-  constexpr int BNK = NWT * 32;  // kv rows per block
+  constexpr int NTH = NTHREADS;
+  constexpr int BNK = NW * 32;  // kv rows per block
   constexpr int KB = BN * D * 2;
   // double-buffered (Q rm | dOT): one barrier per q tile
   __shared__ __attribute__((aligned(16))) char smem[2 * (2 * KB)];
@@ -586,8 +634,8 @@ __global__ __launch_bounds__(NWT * WAVE) void attn_bwd_dv_kernel(
   }
 }
 
-template <int D, bool CAUSAL, int NWT = NW>
-__global__ __launch_bounds__(NWT * WAVE) void attn_bwd_dk_kernel(
+template <int D, bool CAUSAL>
+__global__ __launch_bounds__(NTHREADS) void attn_bwd_dk_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
     const bf16_t* __restrict__ q_t, const float* __restrict__ lse,
@@ -595,8 +643,8 @@ __global__ __launch_bounds__(NWT * WAVE) void attn_bwd_dk_kernel(
     int Hq, int Hkv, int S_pad, float scale) {
   constexpr int QC = D / 16;
   constexpr int DT = D / 32;
-  constexpr int NTH = NWT * WAVE;
-  constexpr int BNK = NWT * 32;
+  constexpr int NTH = NTHREADS;
+  constexpr int BNK = NW * 32;
   constexpr int KB = BN * D * 2;
   // Q rm | QT | dO rm | V block tile (staged once; keeping V in
   // registers alongside K pushed the kernel to 256 VGPR + scratch spill)
@@ -743,6 +791,388 @@ __global__ __launch_bounds__(NWT * WAVE) void attn_bwd_dk_kernel(
 }
 
 // ========================================================================
+// Backward dK+dV FUSED: grid (ceil(S/256), Hkv, B); 4 waves, 1 wave/SIMD,
+// wave = 64 keys as two 32-key halves. S = Q·K^T, its exp and its mask are
+// computed once for both outputs, and every Q/dO/Q^T/dO^T fragment read
+// from LDS feeds two MFMAs (one per half); the two halves are independent
+// MFMA chains, which is the latency hiding the second wave per SIMD gives
+// the split kernels. dK^T and dV^T of the wave's 64 keys live in 256
+// accumulator registers for the whole sweep over rep heads x q tiles.
+//
+// Row constants ride in the accumulators: S starts at -lse*sqrt(D) and dP
+// at -Dsum, so p = exp2(S' * log2(e)/sqrt(D)) and dS = p * dP' need no
+// per-element shuffle, subtract or row maximum. A row's start value
+// depends only on (r, hi) - four runs of four consecutive rows - so it is
+// 4 b128 reads per operand from a 256-byte LDS copy staged with the tile.
+// The start values come ready-made from attn_bwd_pre_kernel ([B,Hq,2,
+// S_pad]): padded q rows and lse == -inf rows hold S' = -1e30, so the
+// exponent goes to -inf and p is exactly 0; only the key side (diagonal,
+// keys >= S) still needs the per-element mask.
+//
+// LDS: a 64-row stage of the four images (Q rm, Q^T, dO rm, dO^T) is
+// 64 KiB; double-buffered next to the block's 64 KiB V tile that is
+// 192 KiB > 160 KiB. Way out taken: 32-ROW STAGES (2 x 32.25 KiB + 64 KiB
+// V = 128.5 KiB). V in registers would cost 64 more VGPRs on top of
+// dK 128 + dV 128 + K 64, and the kernel already sits at 512; the single
+// dual-use image (tr-reads) needs an operand layout nothing here has
+// verified on hardware. The pre-transposed Q^T/dO^T planes are kept.
+//
+// Staging: at 1 wave/SIMD nothing else covers a global load's latency, so
+// the next stage must be in flight for a whole tile, and a register ring
+// that deep (33 VGPRs) does not fit. The stage is loaded global -> LDS by
+// DMA instead (DkdvStage): issued at the top of a tile into the idle
+// buffer, retired with vmcnt(0) just before the tile's barrier. Measured
+// on the whole backward at B=8 S=4096: register ring split in two halves
+// 10.1 ms, DMA 9.4 ms (split dV/dK pair 12.9 ms); profiles/attn_dkdv.log.
+// ========================================================================
+constexpr int NW_KV = 4;              // waves per block in the fused kernel
+constexpr int NTH_KV = NW_KV * WAVE;  // 256
+constexpr int QROWS = 32;             // q rows per stage
+
+// Inverse of swz_off: the (row, byte-in-row) whose swizzled offset is o.
+DEVINL void unswz(int o, int row_bytes, int& row, int& byte_in_row) {
+  const int k = 256 / row_bytes;   // rows per 256-byte XOR group
+  const int base = (o >> 8) * k;
+  row = base;
+  byte_in_row = 0;
+  for (int rl = 0; rl < k; ++rl) {
+    const int r = base + rl;
+    const int x = o ^ ((r & 15) << 4);
+    if (x / row_bytes == r) {
+      row = r;
+      byte_in_row = x - r * row_bytes;
+    }
+  }
+}
+
+// BYTES-per-lane global -> LDS DMA: lane i's bytes land at
+// lds_wave_base + BYTES*i. Inline asm, with M0 (the DMA's LDS base) saved
+// and restored: the compiler then does not see an LDS write it would
+// order every later ds_read behind with vmcnt(0); DkdvStage::finish()
+// and the block barrier do that ordering instead.
+template <int BYTES>
+DEVINL void glds(const void* g, char* lds_wave_base) {
+  static_assert(BYTES == 16 || BYTES == 4, "dwordx4 or dword");
+  const uint32_t dst = __builtin_amdgcn_readfirstlane(
+      (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)
+          lds_wave_base);
+  uint32_t keep;
+  if (BYTES == 16)
+    asm volatile(
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(g), "s"(dst)
+        : "memory");
+  else
+    asm volatile(
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+        "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(g), "s"(dst)
+        : "memory");
+}
+
+// One stage = the four [32 q rows] images + 64 row constants. The images
+// go global -> LDS directly (global_load_lds_dwordx4, no staging
+// registers: the kernel is at the register cap). A wave-instruction
+// writes 64 x 16 B linearly, so the swizzle is applied on the SOURCE
+// side: the lane that lands on LDS offset o loads the chunk whose
+// swz_off is o. Rows past S re-read row S-1 (finite data; their P and dS
+// are exactly 0 through the row constant) since a DMA cannot write
+// zeros.
+template <int D>
+struct DkdvStage {
+  static constexpr int VPR = D / 8;                 // 16B vecs per rm row
+  static constexpr int NV = QROWS * VPR / NTH_KV;   // vecs/thread/image
+  static constexpr int TB = QROWS * D * 2;          // bytes per image
+  static constexpr int RC_OFF = 4 * TB;             // 32 S' + 32 dP' starts
+  static constexpr int BYTES = 4 * TB + 256;
+  // source of this lane's first chunk per image; chunk i is 4096 LDS
+  // bytes on = a whole number of 16-row groups further down, so its
+  // swizzle and column are the same
+  static constexpr int RM_STEP = NTH_KV * 16 / (D * 2);   // rows
+  static constexpr int T_STEP = NTH_KV * 16 / 64;         // d rows
+  static_assert(RM_STEP % 16 == 0 && T_STEP % 16 == 0, "swizzle period");
+  int row_rm, col_rm, off_t;
+
+  DEVINL void init(int S_pad) {
+    const int o = threadIdx.x * 16;
+    int r, bb;
+    unswz(o, D * 2, r, bb);
+    row_rm = r;
+    col_rm = bb >> 1;
+    unswz(o, 64, r, bb);
+    off_t = r * S_pad + (bb >> 1);
+  }
+
+  // pointers at the (b, hq) head; rcp = the head's [2][S_pad] start
+  // values (attn_bwd_pre_kernel); st = destination stage buffer. The
+  // transposed planes and rcp are padded to S_pad >= m0 + 32.
+  DEVINL void issue(const bf16_t* qp, const bf16_t* dop, const bf16_t* qtp,
+                    const bf16_t* dotp, const float* rcp, int m0, int S,
+                    long q_tok, int S_pad, char* st) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      char* dst = st + (i * NTH_KV + (threadIdx.x & ~63)) * 16;
+      const long go =
+          (long)min(m0 + row_rm + i * RM_STEP, S - 1) * q_tok + col_rm;
+      const long to = (long)off_t + (long)i * T_STEP * S_pad + m0;
+      glds<16>(qp + go, dst);
+      glds<16>(dop + go, dst + TB);
+      glds<16>(qtp + to, dst + 2 * TB);
+      glds<16>(dotp + to, dst + 3 * TB);
+    }
+    if (threadIdx.x < 64)   // wave 0: 32 S' starts, then 32 dP' starts
+      glds<4>(rcp + (threadIdx.x >> 5) * S_pad + m0 + (threadIdx.x & 31),
+              st + RC_OFF);
+  }
+
+  // retire this wave's DMAs; the caller's barrier makes the stage
+  // readable
+  DEVINL void finish() const {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+};
+
+// One 32-row q tile against the wave's first NH live 32-key halves, in
+// two parts so the caller can turn the prefetch registers over between
+// them. Part 1: S' = Q·K^T - lse*sqrt(D) and dP' = dO·V^T - Dsum.
+template <int D, int NH>
+DEVINL void dkdv_tile_sdp(const char* st, const char* v_lds,
+                          const bf16x8v (&k_reg)[2][D / 16],
+                          f32x16 (&sv)[2], f32x16 (&dpv)[2], int vrow0,
+                          int lane, int hi) {
+  constexpr int QC = D / 16;
+  constexpr int TB = DkdvStage<D>::TB;
+  const char* q_lds = st;
+  const char* do_lds = st + TB;
+  const char* rc_lds = st + DkdvStage<D>::RC_OFF;
+
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const f32x4 s4 = *(const f32x4*)(rc_lds + (8 * g + 4 * hi) * 4);
+    const f32x4 d4 = *(const f32x4*)(rc_lds + 128 + (8 * g + 4 * hi) * 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int hh = 0; hh < NH; ++hh) {
+        sv[hh][4 * g + j] = s4[j];
+        dpv[hh][4 * g + j] = d4[j];
+      }
+  }
+#pragma unroll
+  for (int c = 0; c < QC; ++c) {
+    const bf16x8v qa =
+        read_bfrag<D * 2>(q_lds, lane & 31, c * 16 + hi * 8);
+    const bf16x8v doa =
+        read_bfrag<D * 2>(do_lds, lane & 31, c * 16 + hi * 8);
+#pragma unroll
+    for (int hh = 0; hh < NH; ++hh) {
+      sv[hh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          qa, k_reg[hh][c], sv[hh], 0, 0, 0);
+      const bf16x8v vb = read_bfrag<D * 2>(
+          v_lds, vrow0 + hh * 32 + (lane & 31), c * 16 + hi * 8);
+      dpv[hh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          doa, vb, dpv[hh], 0, 0, 0);
+    }
+  }
+}
+
+// Part 2: P = exp2(c2*S'), dS = P*dP', dV += P^T·dO, dK += dS^T·Q.
+template <int D, bool CAUSAL, int NH>
+DEVINL void dkdv_tile_acc(const char* st, const f32x16 (&sv)[2],
+                          const f32x16 (&dpv)[2],
+                          f32x16 (&dk_acc)[2][D / 32],
+                          f32x16 (&dv_acc)[2][D / 32], int m0, int n0w,
+                          int S, int lane, int hi, float c2) {
+  constexpr int DT = D / 32;
+  constexpr int TB = DkdvStage<D>::TB;
+  const char* qt_lds = st + 2 * TB;
+  const char* dot_lds = st + 3 * TB;
+
+  bf16x8v pa[NH][2], da[NH][2];
+#pragma unroll
+  for (int hh = 0; hh < NH; ++hh) {
+    const int ks0 = n0w + hh * 32;
+    const int kvrow = ks0 + (lane & 31);
+    // q-side padding is already in the row constant; only the diagonal
+    // and the key tail need the per-element mask (uniform flag)
+    const bool need_mask = (CAUSAL && m0 < ks0 + 32) || (ks0 + 32 > S);
+    f32x16 pt, dst;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float pv = __builtin_amdgcn_exp2f(sv[hh][r] * c2);
+      if (need_mask) {
+        const int qg = m0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        if (!(kvrow < S && (!CAUSAL || qg >= kvrow))) pv = 0.f;
+      }
+      pt[r] = pv;
+      dst[r] = pv * dpv[hh][r];
+    }
+    repack_pa(pt, pa[hh][0], pa[hh][1]);
+    repack_pa(dst, da[hh][0], da[hh][1]);
+  }
+
+#pragma unroll
+  for (int t = 0; t < DT; ++t) {
+    const bf16x8v o0 = read_bfrag<64>(dot_lds, t * 32 + (lane & 31), hi * 8);
+    const bf16x8v q0 = read_bfrag<64>(qt_lds, t * 32 + (lane & 31), hi * 8);
+    const bf16x8v o1 =
+        read_bfrag<64>(dot_lds, t * 32 + (lane & 31), 16 + hi * 8);
+    const bf16x8v q1 =
+        read_bfrag<64>(qt_lds, t * 32 + (lane & 31), 16 + hi * 8);
+#pragma unroll
+    for (int hh = 0; hh < NH; ++hh) {
+      dv_acc[hh][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          pa[hh][0], o0, dv_acc[hh][t], 0, 0, 0);
+      dk_acc[hh][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          da[hh][0], q0, dk_acc[hh][t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int hh = 0; hh < NH; ++hh) {
+      dv_acc[hh][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          pa[hh][1], o1, dv_acc[hh][t], 0, 0, 0);
+      dk_acc[hh][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          da[hh][1], q1, dk_acc[hh][t], 0, 0, 0);
+    }
+  }
+}
+
+template <int D, bool CAUSAL>
+__global__ __launch_bounds__(NTH_KV) void attn_bwd_dkdv_kernel(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+    const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
+    const bf16_t* __restrict__ q_t, const bf16_t* __restrict__ dot_t,
+    const float* __restrict__ rc, bf16_t* __restrict__ dk,
+    bf16_t* __restrict__ dv, int B, int S, int Hq, int Hkv, int S_pad,
+    float scale) {
+  constexpr int QC = D / 16;
+  constexpr int DT = D / 32;
+  constexpr int BNK = NW_KV * 64;   // 256 keys per block
+  constexpr int STB = DkdvStage<D>::BYTES;
+  __shared__ __attribute__((aligned(16))) char smem[2 * STB + BNK * D * 2];
+  char* v_lds = smem + 2 * STB;
+
+  const int lane = threadIdx.x & 63;
+  const int hi = lane >> 5;
+  const int wid = threadIdx.x >> 6;
+  const int n0 = blockIdx.x * BNK;
+  const int n0w = n0 + wid * 64;
+  const int hkv = blockIdx.y;
+  const int b = blockIdx.z;
+  const int rep = Hq / Hkv;
+
+  const long q_tok = (long)Hq * D, kv_tok = (long)Hkv * D;
+  const bf16_t* kp = k + ((long)b * S * kv_tok) + (long)hkv * D;
+  const bf16_t* vp = v + ((long)b * S * kv_tok) + (long)hkv * D;
+
+  bf16x8v k_reg[2][QC];
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh) {
+    const int kvrow = n0w + hh * 32 + (lane & 31);
+#pragma unroll
+    for (int c = 0; c < QC; ++c) {
+      uint4 kr = {0, 0, 0, 0};
+      if (kvrow < S)
+        kr = *(const uint4*)(kp + (long)kvrow * kv_tok + c * 16 + hi * 8);
+      k_reg[hh][c] = as_frag(kr);
+    }
+  }
+  {  // stage the block's 256-row V tile (row-major, swizzled) once
+    constexpr int VPR = D / 8;
+#pragma unroll 4
+    for (int vi = threadIdx.x; vi < BNK * VPR; vi += NTH_KV) {
+      const int row = vi / VPR, cv = vi % VPR;
+      uint4 val = {0, 0, 0, 0};
+      if (n0 + row < S)
+        val = *(const uint4*)(vp + (long)(n0 + row) * kv_tok + cv * 8);
+      *(uint4*)(v_lds + swz_off(row, D * 2, cv * 16)) = val;
+    }
+  }
+
+  f32x16 dk_acc[2][DT], dv_acc[2][DT];
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+    for (int t = 0; t < DT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        dk_acc[hh][t][r] = 0.f;
+        dv_acc[hh][t][r] = 0.f;
+      }
+
+  const int m_start = CAUSAL ? n0 : 0;   // n0 is a multiple of QROWS
+  const float c2 = 1.4426950408889634f * scale;
+  const long plane = (long)D * S_pad;
+  const long head0 = (long)b * Hq + hkv * rep;
+  const bf16_t* qh = q + ((long)b * S * q_tok) + (long)(hkv * rep) * D;
+  const bf16_t* doh = dout + ((long)b * S * q_tok) + (long)(hkv * rep) * D;
+
+  DkdvStage<D> stg;
+  stg.init(S_pad);
+  stg.issue(qh, doh, q_t + head0 * plane, dot_t + head0 * plane,
+            rc + head0 * 2 * S_pad, m_start, S, q_tok, S_pad, smem);
+  stg.finish();
+  __syncthreads();
+  int cur = 0;
+
+  for (int g = 0; g < rep; ++g) {
+    for (int m0 = m_start; m0 < S; m0 += QROWS) {
+      const char* st = smem + cur * STB;
+      char* nst = smem + (cur ^ 1) * STB;
+      // next tile: next q rows of this head, else the next head's first
+      int gn = g, mn = m0 + QROWS;
+      if (mn >= S) {
+        gn = g + 1;
+        mn = m_start;
+      }
+      const bool more = gn < rep;
+      // wave-uniform skip of key halves with no keys or entirely above
+      // the diagonal for this q tile; half 1 live implies half 0 live
+      const bool live0 = n0w < S && (!CAUSAL || m0 + QROWS > n0w);
+      const bool live1 =
+          n0w + 32 < S && (!CAUSAL || m0 + QROWS > n0w + 32);
+
+      // the other buffer was last read before the previous barrier
+      if (more)
+        stg.issue(qh + (long)gn * D, doh + (long)gn * D,
+                  q_t + (head0 + gn) * plane, dot_t + (head0 + gn) * plane,
+                  rc + (head0 + gn) * 2 * S_pad, mn, S, q_tok, S_pad, nst);
+      f32x16 sv[2], dpv[2];
+      if (live1) {
+        dkdv_tile_sdp<D, 2>(st, v_lds, k_reg, sv, dpv, wid * 64, lane, hi);
+        dkdv_tile_acc<D, CAUSAL, 2>(st, sv, dpv, dk_acc, dv_acc, m0, n0w, S,
+                                    lane, hi, c2);
+      } else if (live0) {
+        dkdv_tile_sdp<D, 1>(st, v_lds, k_reg, sv, dpv, wid * 64, lane, hi);
+        dkdv_tile_acc<D, CAUSAL, 1>(st, sv, dpv, dk_acc, dv_acc, m0, n0w, S,
+                                    lane, hi, c2);
+      }
+      if (more) stg.finish();
+      __syncthreads();
+      cur ^= 1;
+    }
+  }
+
+  bf16_t* dkp = dk + ((long)b * S * kv_tok) + (long)hkv * D;
+  bf16_t* dvp = dv + ((long)b * S * kv_tok) + (long)hkv * D;
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = n0w + hh * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      if (row >= S) continue;
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        const long off = (long)row * kv_tok + t * 32 + (lane & 31);
+        dkp[off] = f2bf(dk_acc[hh][t][r] * scale);
+        dvp[off] = f2bf(dv_acc[hh][t][r]);
+      }
+    }
+}
+
+// ========================================================================
 // Backward dQ v3: grid (ceil(S/256), Hq, B); 8 waves, wave = 32 q rows.
 // Q/dO in registers (lane owns q row); lse/Dsum are per-lane scalars.
 // ========================================================================
@@ -763,7 +1193,11 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
   const int lane = threadIdx.x & 63;
   const int hi = lane >> 5;
   const int wid = threadIdx.x >> 6;
-  const int m0 = blockIdx.x * BM3;
+  // causal: the last q block has the most kv tiles; dispatch it first so
+  // the grid does not end on a tail of 16-tile blocks (measured -3 % on
+  // the whole backward, docs/ROADMAP.md)
+  const int m0 =
+      (CAUSAL ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x) * BM3;
   const int m0w = m0 + wid * 32;
   const int hq = blockIdx.y;
   const int b = blockIdx.z;
@@ -941,46 +1375,34 @@ hipError_t tok_attn_fwd(const void* q, const void* k, const void* vt, void* o,
 }
 
 // q_t/k_t/dot_t: pre-transposed [.., D, S_pad] planes (tok_transpose_head)
+// split = 0: pre -> fused dK+dV -> dQ (default); split = 1: pre -> dV ->
+// dK -> dQ with the 8-wave split kernels, kept so both paths can be timed
+// and compared in one process.
 hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
                         const void* o, const void* dout, const void* q_t,
                         const void* k_t, const void* dot_t, const float* lse,
-                        float* dsum_ws, void* dq, void* dk, void* dv, int B,
-                        int S, int Hq, int Hkv, int D, int S_pad, int causal,
-                        hipStream_t stream) {
+                        float* dsum_ws, float* rc_ws, void* dq, void* dk,
+                        void* dv, int B, int S, int Hq, int Hkv, int D,
+                        int S_pad, int causal, hipStream_t stream, int split) {
   const float scale = 1.f / sqrtf((float)D);
-  const long rows = (long)B * S * Hq;
-  long pgrid = (rows + 255) / 256;
-  if (pgrid > 4096) pgrid = 4096;
+  dim3 gpre((S + PRE_ROWS - 1) / PRE_ROWS, Hq, B);
   if (D == 128)
-    attn_bwd_pre_kernel<128><<<(int)pgrid, 256, 0, stream>>>(
-        (const bf16_t*)dout, (const bf16_t*)o, dsum_ws, rows, Hq, S);
+    attn_bwd_pre_kernel<128><<<gpre, 256, 0, stream>>>(
+        (const bf16_t*)dout, (const bf16_t*)o, lse, dsum_ws, rc_ws, Hq, S,
+        S_pad, 1.f / scale);
   else if (D == 64)
-    attn_bwd_pre_kernel<64><<<(int)pgrid, 256, 0, stream>>>(
-        (const bf16_t*)dout, (const bf16_t*)o, dsum_ws, rows, Hq, S);
+    attn_bwd_pre_kernel<64><<<gpre, 256, 0, stream>>>(
+        (const bf16_t*)dout, (const bf16_t*)o, lse, dsum_ws, rc_ws, Hq, S,
+        S_pad, 1.f / scale);
   else
     return hipErrorInvalidValue;
 
   dim3 gkv((S + NW * 32 - 1) / (NW * 32), Hkv, B);
-  dim3 gkv4((S + 4 * 32 - 1) / (4 * 32), Hkv, B);
+  dim3 gkvf((S + NW_KV * 64 - 1) / (NW_KV * 64), Hkv, B);
   dim3 gq((S + NW * 32 - 1) / (NW * 32), Hq, B);
-  // dv/dk block-shape A/B: TOK_BWD_NW4=1 runs 4-wave blocks (two
-  // resident per CU -> cross-block phase drift on each SIMD)
-  static const bool nw4 = [] {
-    const char* e = getenv("TOK_BWD_NW4");
-    return e && e[0] == '1';
-  }();
 #define LAUNCH_BWD(DD, CC)                                                    \
   do {                                                                        \
-    if (nw4) {                                                                \
-      attn_bwd_dv_kernel<DD, CC, 4><<<gkv4, 4 * WAVE, 0, stream>>>(           \
-          (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)dot_t,           \
-          (const bf16_t*)dout, lse, dsum_ws, (bf16_t*)dv, B, S, Hq, Hkv,     \
-          S_pad, scale);                                                      \
-      attn_bwd_dk_kernel<DD, CC, 4><<<gkv4, 4 * WAVE, 0, stream>>>(           \
-          (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,               \
-          (const bf16_t*)dout, (const bf16_t*)q_t, lse, dsum_ws,              \
-          (bf16_t*)dk, B, S, Hq, Hkv, S_pad, scale);                          \
-    } else {                                                                  \
+    if (split) {                                                              \
       attn_bwd_dv_kernel<DD, CC><<<gkv, NTHREADS, 0, stream>>>(               \
           (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)dot_t,           \
           (const bf16_t*)dout, lse, dsum_ws, (bf16_t*)dv, B, S, Hq, Hkv,     \
@@ -989,6 +1411,11 @@ hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
           (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,               \
           (const bf16_t*)dout, (const bf16_t*)q_t, lse, dsum_ws,              \
           (bf16_t*)dk, B, S, Hq, Hkv, S_pad, scale);                          \
+    } else {                                                                  \
+      attn_bwd_dkdv_kernel<DD, CC><<<gkvf, NTH_KV, 0, stream>>>(              \
+          (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,               \
+          (const bf16_t*)dout, (const bf16_t*)q_t, (const bf16_t*)dot_t,      \
+          rc_ws, (bf16_t*)dk, (bf16_t*)dv, B, S, Hq, Hkv, S_pad, scale);      \
     }                                                                         \
     attn_bwd_dq_kernel<DD, CC><<<gq, NTHREADS, 0, stream>>>(                  \
         (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,                 \

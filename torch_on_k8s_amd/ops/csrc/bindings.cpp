@@ -55,9 +55,9 @@ hipError_t tok_attn_fwd(const void* q, const void* k, const void* vt, void* o,
 hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
                         const void* o, const void* dout, const void* q_t,
                         const void* k_t, const void* dot_t, const float* lse,
-                        float* dsum_ws, void* dq, void* dk, void* dv, int B,
-                        int S, int Hq, int Hkv, int D, int S_pad, int causal,
-                        hipStream_t stream);
+                        float* dsum_ws, float* rc_ws, void* dq, void* dk,
+                        void* dv, int B, int S, int Hq, int Hkv, int D,
+                        int S_pad, int causal, hipStream_t stream, int split);
 hipError_t tok_transpose_head(const void* in, void* out, int B, int S, int H,
                               int D, int S_pad, hipStream_t stream);
 hipError_t tok_attn_decode(const void* q, const void* k, const void* v,
@@ -310,9 +310,11 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   return {o, lse};
 }
 
+// split = false: fused dK+dV kernel (default); true: the older split
+// dV / dK kernels, for A/B timing and cross-checks in one process.
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor o, at::Tensor lse, at::Tensor dout,
-                                 bool causal) {
+                                 bool causal, bool split) {
   CHECK_BF16_CUDA(q);
   CHECK_BF16_CUDA(dout);
   const int B = q.size(0), S = q.size(1), Hq = q.size(2), D = q.size(3);
@@ -322,6 +324,9 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
   auto dv = at::empty_like(v);
   auto dsum = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
   const int S_pad = (S + 63) / 64 * 64;
+  // start values of the fused kernel's S / dP accumulators, written by
+  // the Dsum preprocess next to dsum
+  auto rc = at::empty({B, Hq, 2, S_pad}, q.options().dtype(at::kFloat));
   auto qt = at::empty({B, Hq, D, S_pad}, q.options());
   auto kt = at::empty({B, Hkv, D, S_pad}, q.options());
   auto dot = at::empty({B, Hq, D, S_pad}, q.options());
@@ -335,8 +340,9 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                           o.data_ptr(), dout.data_ptr(), qt.data_ptr(),
                           kt.data_ptr(), dot.data_ptr(),
                           lse.data_ptr<float>(), dsum.data_ptr<float>(),
-                          dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S,
-                          Hq, Hkv, D, S_pad, causal ? 1 : 0, current_stream()));
+                          rc.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S,
+                          Hq, Hkv, D, S_pad, causal ? 1 : 0, current_stream(),
+                          split ? 1 : 0));
   return {dq, dk, dv};
 }
 
@@ -449,7 +455,10 @@ at::Tensor mfma_probe(at::Tensor A, at::Tensor B) {
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("mfma_probe", &mfma_probe, "MFMA 16x16x32 bf16 layout probe");
   mod.def("attn_fwd", &attn_fwd, "Flash attention forward (bf16, gfx950)");
-  mod.def("attn_bwd", &attn_bwd, "Flash attention backward (bf16, gfx950)");
+  mod.def("attn_bwd", &attn_bwd, "Flash attention backward (bf16, gfx950)",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+          py::arg("lse"), py::arg("dout"), py::arg("causal"),
+          py::arg("split") = false);
   mod.def("ce_fwd", &ce_fwd, "Fused cross-entropy forward (bf16, gfx950)");
   mod.def("layernorm_fwd", &layernorm_fwd, "LayerNorm forward (bf16, gfx950)");
   mod.def("attn_decode", &attn_decode,
