@@ -36,11 +36,15 @@ class TrainerConfig:
     weight_decay: float = 0.1
     betas: tuple = (0.9, 0.95)
     grad_clip: float = 0.0          # 0 disables (extra HBM pass when on)
+    clip_on_device: bool = False    # norm + clip coefficient via the HIP
+                                    # reduction kernels: no fp32 temporary,
+                                    # no host sync (implied by hip_graph)
     bucket_mb: int = 256
     activation_checkpointing: bool = False
     overlap_grad_sync: bool = True
     hip_graph: bool = False          # capture the whole step in a hipGraph
-                                     # and replay it (needs grad_clip=0)
+                                     # and replay it (single GPU; clip, LR
+                                     # schedule and accumulation supported)
     dtype: str = "bf16"             # compute dtype on GPU
     seed: int = 1234
     metrics_path: str | None = None  # structured metrics for the elastic
@@ -89,12 +93,17 @@ class Trainer:
         self._t_last = None
         self._graph = None
         self._graph_state = None
+        # Clip on device: the reduction kernels leave [norm, gscale] in
+        # device memory and AdamW reads gscale from there. A captured step
+        # cannot do it any other way (the host path needs coef.item()).
+        self._clip_dev = cfg.grad_clip > 0 and \
+            (cfg.clip_on_device or cfg.hip_graph)
+        if self._clip_dev:
+            self.fb.alloc_norm_workspace()  # once, outside any capture
+        self._lr_dev = None     # scheduled LR under hip_graph (device fp32)
+        self._last_lr = None    # host LR of the last step (metrics)
+        self._last_norm = None  # device norm of the last step
         if cfg.hip_graph:
-            assert cfg.grad_clip == 0, "hip_graph requires grad_clip=0"
-            assert cfg.grad_accum_steps <= 1, \
-                "hip_graph does not support gradient accumulation yet"
-            assert not cfg.lr_warmup_steps and not cfg.lr_decay_steps, \
-                "hip_graph freezes the captured LR; schedules need eager"
             # Capturing RCCL collectives inside a hipGraph has known
             # constraints (NCCL watchdog/capture-mode interactions) and
             # has never executed on multi-GPU hardware in this repo —
@@ -110,6 +119,11 @@ class Trainer:
                     "override after validating capture+replay on your "
                     "node, or run hip_graph on a single GPU")
             assert self.device.type == "cuda", "hip_graph needs a GPU"
+            if cfg.lr_warmup_steps or cfg.lr_decay_steps:
+                # a host LR would be frozen into the capture: AdamW reads
+                # this scalar instead and the host refills it every step
+                self._lr_dev = torch.zeros((), dtype=torch.float32,
+                                           device=self.device)
 
     @property
     def module(self):
@@ -137,12 +151,23 @@ class Trainer:
             loss.backward()
         self.fb.finish_grad_sync()
         scale = 1.0 / (self.fb.world_size * accum)
-        if self.cfg.grad_clip > 0:
-            norm = self.fb.grad_norm() / accum
-            coef = self.cfg.grad_clip / (norm + 1e-6)
-            coef = torch.clamp(coef, max=1.0)
-            scale = scale * coef.item()
-        self.opt.step(grad_scale=scale, lr=self.current_lr())
+        lr = self.current_lr()
+        if self._clip_dev:
+            # same arithmetic as below, in two kernels: the coefficient
+            # never visits the host and no fp32 copy of the grads is made
+            out = self.fb.device_grad_norm(inv_count=scale,
+                                           clip=self.cfg.grad_clip)
+            self._last_norm = out[0]
+            self.opt.step(grad_scale=scale, lr=lr, gscale_dev=out[1:])
+        else:
+            if self.cfg.grad_clip > 0:
+                norm = self.fb.grad_norm() / accum
+                coef = self.cfg.grad_clip / (norm + 1e-6)
+                coef = torch.clamp(coef, max=1.0)
+                scale = scale * coef.item()
+                self._last_norm = norm
+            self.opt.step(grad_scale=scale, lr=lr)
+        self._last_lr = lr
         self.step_count += 1
         if not sync:
             return loss.detach()
@@ -157,16 +182,32 @@ class Trainer:
     # optimizer's on-device step counter so replay stays correct) ------
     def _capture_graph(self):
         cfg = self.cfg
-        inp = torch.zeros(cfg.micro_batch, cfg.seq_len, dtype=torch.long,
-                          device=self.device)
+        accum = max(1, cfg.grad_accum_steps)
+        # staging buffers: one slot per micro-batch of the step
+        inp = torch.zeros(accum, cfg.micro_batch, cfg.seq_len,
+                          dtype=torch.long, device=self.device)
         lab = torch.zeros_like(inp)
+        self._graph_state = (inp, lab, None)
+        inv = 1.0 / (self.fb.world_size * accum)
 
         def step_body():
             self.fb.zero_grads()
-            loss = self.fb(inp, lab)
-            loss.backward()
+            loss = None
+            for micro in range(accum):
+                self.fb.set_accumulate(micro < accum - 1)
+                loss = self.fb(inp[micro], lab[micro])
+                loss.backward()
             self.fb.finish_grad_sync()
-            self.opt.step()
+            gscale_dev = None
+            if self._clip_dev:
+                out = self.fb.device_grad_norm(inv_count=inv,
+                                               clip=cfg.grad_clip)
+                self._last_norm = out[0]
+                gscale_dev = out[1:]
+            # no clip, no schedule, accum 1: the launches and arguments of
+            # a bare opt.step()
+            self.opt.step(grad_scale=inv, lr_dev=self._lr_dev,
+                          gscale_dev=gscale_dev)
             return loss
 
         # Warm up allocator/RCCL/hook state on a side stream. These are
@@ -175,9 +216,7 @@ class Trainer:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(2):
-                ni, nl = self.data.batch(self.step_count)
-                inp.copy_(ni)
-                lab.copy_(nl)
+                self._stage_step()
                 step_body()
                 self.step_count += 1
         torch.cuda.current_stream().wait_stream(side)
@@ -188,14 +227,28 @@ class Trainer:
         self._graph = g
         self._graph_state = (inp, lab, loss)
 
+    def _stage_step(self):
+        """Host-side inputs of the next captured step, written outside the
+        graph with plain async copies (no sync): the micro-batches and,
+        when a schedule is set, the LR. The schedule itself stays in
+        Python (current_lr)."""
+        inp, lab, _ = self._graph_state
+        accum = inp.shape[0]
+        for micro in range(accum):
+            ni, nl = self.data.batch(self.step_count * accum + micro)
+            inp[micro].copy_(ni)
+            lab[micro].copy_(nl)
+        lr = self.current_lr()
+        if self._lr_dev is not None:
+            self._lr_dev.fill_(lr)
+        self._last_lr = lr
+
     def _train_step_graph(self, sync: bool):
         t0 = time.perf_counter()
         if self._graph is None:
             self._capture_graph()
-        inp, lab, loss = self._graph_state
-        ni, nl = self.data.batch(self.step_count)
-        inp.copy_(ni)
-        lab.copy_(nl)
+        loss = self._graph_state[2]
+        self._stage_step()
         self._graph.replay()
         self.step_count += 1
         if not sync:
@@ -221,6 +274,13 @@ class Trainer:
             return floor + (lr - floor) * 0.5 * (1 + math.cos(math.pi * t))
         return lr
 
+    def last_grad_norm(self) -> torch.Tensor | None:
+        """Global norm of the averaged gradients the last step clipped
+        against, as a 0-dim device tensor (reading it syncs; under
+        hip_graph it is rewritten by every replay). None when grad_clip
+        is off or before the first step."""
+        return self._last_norm
+
     def tokens_per_step(self) -> int:
         return self.cfg.micro_batch * self.cfg.seq_len * \
             self.fb.world_size * max(1, self.cfg.grad_accum_steps)
@@ -238,6 +298,11 @@ class Trainer:
             "world_size": self.fb.world_size,
             "ts": time.time(),
         }
+        if self.cfg.grad_clip > 0 and self._last_norm is not None:
+            # only reached from the sync=True path, which has just synced
+            # for the loss: reading the device norm costs nothing extra
+            rec["grad_norm"] = float(self._last_norm)
+            rec["lr"] = self._last_lr
         tmp = self.cfg.metrics_path + ".tmp"
         with open(tmp, "w") as f:
             json.dump(rec, f)

@@ -260,17 +260,27 @@ def fused_adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
                  v: torch.Tensor, *, lr: float, beta1: float, beta2: float,
                  eps: float, weight_decay: float, step: int,
                  grad_scale: float = 1.0,
-                 step_dev: torch.Tensor | None = None) -> None:
+                 step_dev: torch.Tensor | None = None,
+                 lr_dev: torch.Tensor | None = None,
+                 gscale_dev: torch.Tensor | None = None) -> None:
     """In-place AdamW over one flat bucket (p/g bf16, m/v fp32).
 
     step_dev: optional int32 device scalar overriding `step` — used under
     hipGraph replay, where host-side scalars are frozen into the graph.
+    lr_dev / gscale_dev: optional fp32 device scalars overriding `lr` and
+    `grad_scale` the same way (scheduled LR; clip coefficient computed by
+    grad_norm_finalize_ without a host sync).
     """
     if p.is_cuda:
         _require_ext("fused_adamw").adamw_(p, g, m, v, lr, beta1, beta2, eps,
                                            weight_decay, step, grad_scale,
-                                           step_dev)
+                                           step_dev, lr_dev=lr_dev,
+                                           gscale_dev=gscale_dev)
         return
+    if lr_dev is not None:
+        lr = float(lr_dev.reshape(-1)[0])
+    if gscale_dev is not None:
+        grad_scale = float(gscale_dev.reshape(-1)[0])
     gf = g.float() * grad_scale
     pf = p.float()
     pf -= lr * weight_decay * pf
@@ -280,6 +290,63 @@ def fused_adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
     bc2 = 1.0 / (1.0 - beta2 ** step)
     pf -= lr * (m * bc1) / ((v * bc2).sqrt() + eps)
     p.copy_(pf.to(p.dtype))
+
+
+# --------------------------------------------------------------------------
+# Global grad norm + clip coefficient, on device (no host sync, capturable)
+# --------------------------------------------------------------------------
+_SUMSQ_BLOCK_ELEMS = 256 * 8   # one bf16x8 vector per thread per sweep
+_SUMSQ_MAX_BLOCKS = 2048       # grid cap, as the AdamW kernel
+
+
+def grad_sumsq_blocks(n: int) -> int:
+    """Partial slots (= blocks) grad_sumsq_ uses for a bucket of n
+    elements. Depends on n alone, so a bucket's launch geometry — and with
+    it the order of every addition — is the same on every step."""
+    return max(1, min(_SUMSQ_MAX_BLOCKS, -(-n // _SUMSQ_BLOCK_ELEMS)))
+
+
+@torch.no_grad()
+def grad_sumsq_(g: torch.Tensor, partials: torch.Tensor) -> None:
+    """Sum of squares of a flat bucket, as per-block fp32 partials.
+
+    Writes EVERY slot of `partials` (1-D fp32, grad_sumsq_blocks(n) slots,
+    caller-owned); their sum is sum(g^2). How the sum is split over the
+    slots is unspecified. g.numel() must be a multiple of 8. Allocates
+    nothing on GPU and never syncs; no atomics, so repeatable bit for bit.
+    """
+    if g.is_cuda:
+        _require_ext("grad_sumsq").grad_sumsq_(g, partials)
+        return
+    assert g.numel() % 8 == 0, "bucket size must be a multiple of 8"
+    partials.zero_()
+    partials[0] = g.float().pow(2).sum()
+
+
+@torch.no_grad()
+def grad_norm_finalize_(partials: torch.Tensor, out: torch.Tensor, *,
+                        inv_count: float, clip: float) -> None:
+    """Fold all buckets' partials into two fp32 scalars:
+
+        out[0] = norm   = sqrt(sum(partials)) * inv_count
+        out[1] = gscale = inv_count * min(1, clip / (norm + 1e-6))
+
+    inv_count is 1/(world*accum); clip <= 0 means no clipping (gscale =
+    inv_count). A non-finite norm propagates into gscale, as on the host
+    path. `out` feeds fused_adamw_(gscale_dev=out[1:]).
+    """
+    if partials.is_cuda:
+        _require_ext("grad_norm_finalize").grad_norm_finalize_(
+            partials, out, float(inv_count), float(clip))
+        return
+    inv = torch.tensor(inv_count, dtype=torch.float32)
+    norm = partials.float().sum().sqrt() * inv
+    coef = torch.ones((), dtype=torch.float32)
+    if clip > 0:
+        coef = torch.clamp(
+            torch.tensor(clip, dtype=torch.float32) / (norm + 1e-6), max=1.0)
+    out[0] = norm
+    out[1] = inv * coef
 
 
 # --------------------------------------------------------------------------
@@ -438,4 +505,5 @@ __all__ = [
     "attention", "attention_ref", "cross_entropy", "layernorm",
     "qkv_rope", "qkv_rope_ref", "swiglu", "swiglu_ref",
     "hip_ext_available",
+    "grad_sumsq_blocks", "grad_sumsq_", "grad_norm_finalize_",
 ]

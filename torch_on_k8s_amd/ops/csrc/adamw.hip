@@ -16,7 +16,15 @@ __global__ void adamw_kernel(bf16x8* __restrict__ p, const bf16x8* __restrict__ 
                              f32x4v* __restrict__ m, f32x4v* __restrict__ v,
                              long nvec, float lr, float beta1, float beta2,
                              float eps, float wd, float bc1, float bc2,
-                             float gscale, const int* __restrict__ step_dev) {
+                             float gscale, const int* __restrict__ step_dev,
+                             const float* __restrict__ lr_dev,
+                             const float* __restrict__ gscale_dev) {
+  // device scalars override their host twins the way step_dev does: the
+  // scheduled LR and the clip coefficient change every step, and a host
+  // value would be frozen into a captured graph (and the clip coefficient
+  // would need a host sync to obtain at all)
+  if (lr_dev != nullptr) lr = *lr_dev;
+  if (gscale_dev != nullptr) gscale = *gscale_dev;
   if (step_dev != nullptr) {
     // hipGraph-replay mode: the step counter lives on-device (a host
     // scalar would be frozen into the captured graph), so the bias
@@ -64,6 +72,7 @@ extern "C" {
 hipError_t tok_adamw(void* p, const void* g, float* m, float* v, long n,
                      float lr, float beta1, float beta2, float eps, float wd,
                      int step, float gscale, const int* step_dev,
+                     const float* lr_dev, const float* gscale_dev,
                      hipStream_t stream) {
   const long nvec = n / 8;
   const float bc1 = 1.f / (1.f - powf(beta1, (float)step));
@@ -73,7 +82,6 @@ hipError_t tok_adamw(void* p, const void* g, float* m, float* v, long n,
   if (grid < 1) grid = 1;
   adamw_kernel<<<(int)grid, BLOCK, 0, stream>>>(
       (bf16x8*)p, (const bf16x8*)g, (f32x4v*)m, (f32x4v*)v, nvec, lr, beta1,
-      beta2, eps, wd, bc1, bc2, gscale, step_dev);
-  return hipGetLastError();
+      beta2, eps, wd, bc1, bc2, gscale, step_dev, lr_dev, gscale_dev);  return hipGetLastError();
 }
 }

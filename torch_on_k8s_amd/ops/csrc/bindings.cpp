@@ -44,7 +44,15 @@ hipError_t tok_rope(const void* x, void* y, const float* cos_tab,
 hipError_t tok_adamw(void* p, const void* g, float* m, float* v, long n,
                      float lr, float beta1, float beta2, float eps, float wd,
                      int step, float gscale, const int* step_dev,
+                     const float* lr_dev, const float* gscale_dev,
                      hipStream_t stream);
+int tok_grad_sumsq_max_blocks();
+int tok_grad_sumsq_blocks(long n);
+hipError_t tok_grad_sumsq(const void* g, long n, float* partials, int nblocks,
+                          hipStream_t stream);
+hipError_t tok_grad_norm_finalize(const float* partials, long count,
+                                  float inv_count, float clip, float* out,
+                                  hipStream_t stream);
 hipError_t tok_mfma_probe_16x16x32(const void* A, const void* B, float* D,
                                    hipStream_t stream);
 hipError_t tok_mfma_probe_32x32x16(const void* A, const void* B, float* D,
@@ -267,9 +275,20 @@ at::Tensor rope(at::Tensor x, at::Tensor cos_tab, at::Tensor sin_tab,
   return y;
 }
 
+const float* dev_f32_scalar(const c10::optional<at::Tensor>& t,
+                            const char* name) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat &&
+                  t->numel() >= 1,
+              name, " must be an fp32 GPU scalar");
+  return t->data_ptr<float>();
+}
+
 void adamw_(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, double lr,
             double beta1, double beta2, double eps, double wd, long step,
-            double gscale, c10::optional<at::Tensor> step_dev) {
+            double gscale, c10::optional<at::Tensor> step_dev,
+            c10::optional<at::Tensor> lr_dev,
+            c10::optional<at::Tensor> gscale_dev) {
   CHECK_BF16_CUDA(p);
   CHECK_BF16_CUDA(g);
   TORCH_CHECK(m.scalar_type() == at::kFloat && v.scalar_type() == at::kFloat);
@@ -281,10 +300,47 @@ void adamw_(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, double lr,
     TORCH_CHECK(step_dev->scalar_type() == at::kInt && step_dev->is_cuda());
     sd = step_dev->data_ptr<int>();
   }
+  const float* lrd = dev_f32_scalar(lr_dev, "lr_dev");
+  const float* gsd = dev_f32_scalar(gscale_dev, "gscale_dev");
   TOK_HIP_OK(tok_adamw(p.data_ptr(), g.data_ptr(), m.data_ptr<float>(),
                        v.data_ptr<float>(), n, (float)lr, (float)beta1,
                        (float)beta2, (float)eps, (float)wd, (int)step,
-                       (float)gscale, sd, current_stream()));
+                       (float)gscale, sd, lrd, gsd, current_stream()));
+}
+
+long grad_sumsq_blocks(long n) { return tok_grad_sumsq_blocks(n); }
+
+long grad_sumsq_max_blocks() { return tok_grad_sumsq_max_blocks(); }
+
+// One fp32 partial per block into the caller's workspace; allocates
+// nothing and does not sync (runs under hipGraph capture).
+void grad_sumsq_(at::Tensor g, at::Tensor partials) {
+  CHECK_BF16_CUDA(g);
+  TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
+                  partials.is_contiguous(),
+              "partials must be a contiguous fp32 GPU tensor");
+  const long n = g.numel();
+  TORCH_CHECK(n % 8 == 0, "bucket size must be a multiple of 8");
+  const long nb = partials.numel();
+  TORCH_CHECK(nb >= 1 && nb <= tok_grad_sumsq_max_blocks(),
+              "partials must hold 1..", tok_grad_sumsq_max_blocks(),
+              " slots (use grad_sumsq_blocks(n))");
+  TOK_HIP_OK(tok_grad_sumsq(g.data_ptr(), n, partials.data_ptr<float>(),
+                            (int)nb, current_stream()));
+}
+
+void grad_norm_finalize_(at::Tensor partials, at::Tensor out, double inv_count,
+                         double clip) {
+  TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
+                  partials.is_contiguous(),
+              "partials must be a contiguous fp32 GPU tensor");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat &&
+                  out.is_contiguous() && out.numel() >= 2,
+              "out must be a contiguous fp32 GPU tensor of >= 2 elements");
+  TOK_HIP_OK(tok_grad_norm_finalize(partials.data_ptr<float>(),
+                                    partials.numel(), (float)inv_count,
+                                    (float)clip, out.data_ptr<float>(),
+                                    current_stream()));
 }
 
 // q: [B,S,Hq,D], k/v: [B,S,Hkv,D] bf16 contiguous -> (o, lse[B,Hq,S] f32)
@@ -489,5 +545,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"),
           py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
           py::arg("wd"), py::arg("step"), py::arg("gscale"),
-          py::arg("step_dev") = py::none());
+          py::arg("step_dev") = py::none(), py::arg("lr_dev") = py::none(),
+          py::arg("gscale_dev") = py::none());
+  mod.def("grad_sumsq_blocks", &grad_sumsq_blocks,
+          "Partial slots grad_sumsq_ needs for a bucket of n elements");
+  mod.def("grad_sumsq_max_blocks", &grad_sumsq_max_blocks,
+          "Grid cap of grad_sumsq_");
+  mod.def("grad_sumsq_", &grad_sumsq_,
+          "Per-block sum of squares of a flat bf16 bucket (gfx950)");
+  mod.def("grad_norm_finalize_", &grad_norm_finalize_,
+          "Sum partials -> {norm, clip-folded grad scale} (gfx950)",
+          py::arg("partials"), py::arg("out"), py::arg("inv_count"),
+          py::arg("clip"));
 }

@@ -116,6 +116,10 @@ class FlatBucketModel:
         # into the flat grads; the all-reduce fires on the final
         # micro-step (set_accumulate(False) before it)
         self.accumulate_only = False
+        # on-device grad norm (alloc_norm_workspace / device_grad_norm)
+        self._norm_ws = None
+        self._norm_parts = None
+        self.norm_out = None
         self._hooks = []
         if self.overlap and self.world_size > 1:
             self._register_hooks()
@@ -186,6 +190,45 @@ class FlatBucketModel:
             total += b.flat_grad.float().pow(2).sum()
         return total.sqrt() / self.world_size
 
+    # -- on-device norm + clip coefficient (no host sync, capturable) --
+    def alloc_norm_workspace(self):
+        """Allocate the per-block partials of every bucket (one flat fp32
+        buffer, bucket after bucket) and the two-float result. Call once,
+        outside any graph capture; the buffers are reused every step."""
+        from torch_on_k8s_amd import ops
+        if self.norm_out is not None:
+            return
+        dev = self.buckets[0].flat_grad.device
+        slots = [ops.grad_sumsq_blocks(b.numel) for b in self.buckets]
+        ws = torch.zeros(sum(slots), dtype=torch.float32, device=dev)
+        self._norm_ws = ws
+        self._norm_parts = list(ws.split(slots))
+        self.norm_out = torch.zeros(2, dtype=torch.float32, device=dev)
+
+    @torch.no_grad()
+    def device_grad_norm(self, *, inv_count: float, clip: float):
+        """grad_norm() and the clip coefficient without leaving the
+        device: per-bucket sum-of-squares kernels, then one finalize that
+        writes norm_out = [norm, gscale] with
+
+            norm   = sqrt(sum g^2) * inv_count     (inv_count = 1/(world*accum))
+            gscale = inv_count * min(1, clip / (norm + 1e-6))
+
+        Call after finish_grad_sync(). Returns norm_out; pass
+        norm_out[1:] to FlatAdamW.step(gscale_dev=)."""
+        from torch_on_k8s_amd import ops
+        if self.norm_out is None:
+            if self.buckets[0].flat_grad.is_cuda and \
+                    torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(
+                    "alloc_norm_workspace() must run before graph capture")
+            self.alloc_norm_workspace()
+        for b, part in zip(self.buckets, self._norm_parts):
+            ops.grad_sumsq_(b.flat_grad, part)
+        ops.grad_norm_finalize_(self._norm_ws, self.norm_out,
+                                inv_count=inv_count, clip=clip)
+        return self.norm_out
+
     def forward(self, *args, **kwargs):
         return self.module(*args, **kwargs)
 
@@ -222,7 +265,12 @@ class FlatAdamW:
                          if str(dev).startswith("cuda") else None)
 
     @torch.no_grad()
-    def step(self, grad_scale: float | None = None, lr: float | None = None):
+    def step(self, grad_scale: float | None = None, lr: float | None = None,
+             *, lr_dev: torch.Tensor | None = None,
+             gscale_dev: torch.Tensor | None = None):
+        """lr_dev / gscale_dev (fp32 device scalars) override lr and
+        grad_scale inside the kernel: values that change every step
+        without a host sync or a re-capture."""
         from torch_on_k8s_amd import ops
         self.step_count += 1
         if self.step_dev is not None:
@@ -237,7 +285,8 @@ class FlatAdamW:
                 beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
                 weight_decay=self.weight_decay if b.decay else 0.0,
                 step=self.step_count, grad_scale=grad_scale,
-                step_dev=self.step_dev)
+                step_dev=self.step_dev, lr_dev=lr_dev,
+                gscale_dev=gscale_dev)
 
     def state_dict(self):
         if self.step_dev is not None:
