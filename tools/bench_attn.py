@@ -2,8 +2,9 @@
 """Attention kernel microbenchmark (dev tool, not the driver contract).
 
 Measures fwd / bwd wall time and effective TFLOP/s of the gfx950 flash
-attention at the flagship shape, A/B against torch SDPA. The backward is
-timed both ways, fused dK+dV (default) and split dV / dK, side by side.
+attention at the flagship shape, A/B against torch SDPA. The forward is
+timed both ways, v4 (default) and the older v3, and so is the backward,
+fused dK+dV (default) and split dV / dK, side by side.
 Within-process interleaved rounds (guide §5.4 rule 24). The flagship
 per-layer shape is --B 8; record runs at both --B 2 and --B 8.
 """
@@ -69,6 +70,9 @@ def main():
         o, lse = ops._C.attn_fwd(q, k, v, True)
         return o, lse
 
+    def hip_fwd_v3():   # older forward kernel (variant 1)
+        return ops._C.attn_fwd(q, k, v, True, 1)
+
     o_, lse_ = hip_fwd()
 
     def hip_bwd():      # fused dK+dV kernel (the default path)
@@ -93,11 +97,14 @@ def main():
 
     for r in range(args.rounds):
         th_f = time_fn(hip_fwd, args.iters)
+        th_f3 = time_fn(hip_fwd_v3, args.iters)
         th_b = time_fn(hip_bwd, args.iters)
         th_bs = time_fn(hip_bwd_split, args.iters)
         if args.no_sdpa:
             print(f"[round {r}] hip fwd {th_f*1e3:7.2f} ms "
                   f"{ffw/th_f/1e12:7.1f} TF"
+                  f" | hip fwd v3 {th_f3*1e3:7.2f} ms "
+                  f"{ffw/th_f3/1e12:7.1f} TF"
                   f" | hip bwd fused {th_b*1e3:7.2f} ms "
                   f"{fbw/th_b/1e12:7.1f} TF"
                   f" | hip bwd split {th_bs*1e3:7.2f} ms "
@@ -106,11 +113,18 @@ def main():
         ts_f = time_fn(sdpa_fwd, args.iters)
         ts_fb = time_fn(sdpa_fwdbwd, args.iters)
         print(f"[round {r}] hip fwd {th_f*1e3:7.2f} ms {ffw/th_f/1e12:7.1f} TF"
+              f" | hip fwd v3 {th_f3*1e3:7.2f} ms {ffw/th_f3/1e12:7.1f} TF"
               f" | hip bwd fused {th_b*1e3:7.2f} ms {fbw/th_b/1e12:7.1f} TF"
               f" | hip bwd split {th_bs*1e3:7.2f} ms {fbw/th_bs/1e12:7.1f} TF"
               f" | sdpa fwd {ts_f*1e3:7.2f} ms {ffw/ts_f/1e12:7.1f} TF"
               f" | sdpa f+b {ts_fb*1e3:7.2f} ms "
               f"{(ffw+fbw)/ts_fb/1e12:7.1f} TF", flush=True)
+
+    # the two forwards against each other
+    o3, lse3 = hip_fwd_v3()
+    print(f"max |O v4 - O v3| = "
+          f"{(o_.float() - o3.float()).abs().max().item():.5f}, "
+          f"max |LSE v4 - LSE v3| = {(lse_ - lse3).abs().max().item():.3e}")
 
     # correctness spot-check vs sdpa
     o_ref = sdpa_fwd().transpose(1, 2)

@@ -1,6 +1,7 @@
 // Flash attention (causal, GQA/MHA) for MI355X (gfx950) - fwd + bwd.
 //
-// Architecture (v3; progression + measurements in profiles/README.md):
+// Architecture (v3/v4; progression + measurements in profiles/README.md;
+// the default forward is attn_fwd_kernel_v4, which keeps this structure):
 //  * mfma_f32_32x32x16_bf16 tiles with SWAPPED operands: S^T = K*Q^T so
 //    each lane owns ONE q row; online softmax is fully in-register (an
 //    in-lane chain + one half-wave shuffle; no cross-lane reduce, no P
@@ -29,8 +30,9 @@
 //    tok_attn_bwd's `split` selector for A/B timing. All kernels: 0
 //    scratch spill.
 //
-// Measured (B=2 S=4096 Hq=32 Hkv=8 D=128 causal, random data): fwd
-// 358-371 TF (parity with torch's aotriton flash); bwd incl. the three
+// Measured (B=2 S=4096 Hq=32 Hkv=8 D=128 causal, random data): fwd v3
+// 358-371 TF (parity with torch's aotriton flash), v4 see
+// profiles/attn_fwd_v4.log; bwd incl. the three
 // operand transposes 292-294 TF fused, 212-214 TF with the split pair
 // (profiles/attn_dkdv.log).
 #include "common.h"
@@ -160,8 +162,36 @@ DEVINL void load_afrags(bf16x8v* frag, const bf16_t* src, long row,
 // ========================================================================
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using bf16x2v = __attribute__((ext_vector_type(2))) __bf16;
+
+// Two floats -> one word of two bf16 (lo in bits 0..15). The vector convert
+// is ONE v_cvt_pk_bf16_f32 with the hardware's round-to-nearest-even; two
+// scalar __float2bfloat16 plus a shift and an or compiled to four
+// instructions per pair for the same bits.
 DEVINL uint32_t pack_bf16(float lo, float hi) {
-  return (uint32_t)f2bfbits(lo) | ((uint32_t)f2bfbits(hi) << 16);
+  const f32x2 f = {lo, hi};
+  union { bf16x2v b; uint32_t u; } c;
+  c.b = __builtin_convertvector(f, bf16x2v);
+  return c.u;
+}
+
+// One 32x32 f32 C-layout strip (P^T or dS^T) -> the next MFMA's two bf16
+// A-fragments: cvt_pk pairs + permlane32_swap (guide T12).
+DEVINL void repack_pa(const f32x16& pt, bf16x8v& pa0, bf16x8v& pa1) {
+  union { uint32_t w[4]; bf16x8v f; } f0, f1;
+  auto sA = __builtin_amdgcn_permlane32_swap(
+      pack_bf16(pt[0], pt[1]), pack_bf16(pt[4], pt[5]), false, false);
+  auto sB = __builtin_amdgcn_permlane32_swap(
+      pack_bf16(pt[2], pt[3]), pack_bf16(pt[6], pt[7]), false, false);
+  f0.w[0] = sA[0]; f0.w[1] = sB[0]; f0.w[2] = sA[1]; f0.w[3] = sB[1];
+  auto sC = __builtin_amdgcn_permlane32_swap(
+      pack_bf16(pt[8], pt[9]), pack_bf16(pt[12], pt[13]), false, false);
+  auto sD = __builtin_amdgcn_permlane32_swap(
+      pack_bf16(pt[10], pt[11]), pack_bf16(pt[14], pt[15]), false, false);
+  f1.w[0] = sC[0]; f1.w[1] = sD[0]; f1.w[2] = sC[1]; f1.w[3] = sD[1];
+  pa0 = f0.f;
+  pa1 = f1.f;
 }
 
 template <int D, bool CAUSAL>
@@ -385,6 +415,264 @@ __global__ __launch_bounds__(NTHREADS) void attn_fwd_kernel_v3(
 }
 
 // ========================================================================
+// Forward v4 (tok_attn_fwd variant 0, the default): v3's structure with
+// less vector work around the same 32 MFMAs per tile.
+//  * The running max m_run is kept in log2 units of the SCALED score, so a
+//    probability is exp2(fma(s, scale*log2e, -m_run)): one v_fma and one
+//    v_exp per score where v3 spends a multiply, a subtract, the multiply
+//    inside __expf and the v_exp. The row max is taken over the raw MFMA
+//    output (scale > 0 keeps the order) and scaled once per lane.
+//  * No per-score `== -inf ? 0` select: a masked score is -inf, the fma
+//    keeps it -inf and exp2(-inf) is 0. Only a running max that is still
+//    -inf (a row that has seen no key yet: rows >= S) would give
+//    -inf - -inf; it is replaced by 0 once per lane per tile.
+//  * K fragments are read ahead of their MFMAs: the first 32-key half's 8
+//    ds_read_b128 are all in flight before its chain and the second half's
+//    are issued one per MFMA of the first (sched_group_barrier); left to
+//    itself the compiler reads one fragment ahead with a wait per MFMA.
+//  * Epilogue: O leaves through the block's own LDS (K|V^T are dead after
+//    the loop's last barrier; 8 waves x 32 rows x 2D bytes is exactly the
+//    double buffer) as whole rows in 16-byte stores; v3 writes 64 two-byte
+//    stores per lane at a row stride. 1/l comes back reg-mapped from four
+//    b128 reads of a 128-byte LDS copy instead of 16 bpermutes.
+// ========================================================================
+constexpr float LOG2E = 1.4426950408889634f;
+constexpr float LN2 = 0.6931471805599453f;
+
+template <int D, bool CAUSAL>
+__global__ __launch_bounds__(NTHREADS) void attn_fwd_kernel_v4(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+    const bf16_t* __restrict__ vt, bf16_t* __restrict__ o,
+    float* __restrict__ lse, int B, int S, int Hq, int Hkv, int S_pad,
+    float scale) {
+  constexpr int QC = D / 16;    // Q B-fragments (k-slots of 16)
+  constexpr int DT = D / 32;    // O col tiles of 32
+  constexpr int BM3 = NW * 32;  // 256 q rows per block
+  constexpr int KB = BN * D * 2;
+  constexpr int OWB = 32 * D * 2;   // a wave's O rows in the epilogue
+  static_assert(NW * OWB <= 2 * (2 * KB), "O staging fits the K|VT buffers");
+  __shared__ __attribute__((aligned(16))) char smem[2 * (2 * KB)];
+
+  const int lane = threadIdx.x & 63;
+  const int hi = lane >> 5;
+  const int wid = threadIdx.x >> 6;
+  const int m0 = blockIdx.x * BM3;
+  const int m0w = m0 + wid * 32;
+  const int hq = blockIdx.y;
+  const int b = blockIdx.z;
+  const int hkv = hq / (Hq / Hkv);
+
+  const long q_tok = (long)Hq * D, kv_tok = (long)Hkv * D;
+  const bf16_t* qp = q + ((long)b * S * q_tok) + (long)hq * D;
+  const bf16_t* kp = k + ((long)b * S * kv_tok) + (long)hkv * D;
+  const bf16_t* vtp = vt + ((long)b * Hkv + hkv) * D * (long)S_pad;
+  bf16_t* op = o + ((long)b * S * q_tok) + (long)hq * D;
+  float* lsep = lse + ((long)b * Hq + hq) * S;
+
+  const int qrow = m0w + (lane & 31);
+  bf16x8v q_reg[QC];
+#pragma unroll
+  for (int c = 0; c < QC; ++c) {
+    uint4 raw = {0, 0, 0, 0};
+    if (qrow < S)
+      raw = *(const uint4*)(qp + (long)qrow * q_tok + c * 16 + hi * 8);
+    q_reg[c] = as_frag(raw);
+  }
+
+  f32x16 o_acc[DT];
+#pragma unroll
+  for (int t = 0; t < DT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o_acc[t][r] = 0.f;
+  // m_run: running row max of score*scale*log2e (log2 units)
+  float m_run = NEG_INF, l_run = 0.f;
+  const float c2 = scale * LOG2E;
+
+  TileStage<D> k_st;
+  TileStageT<D> v_st;
+  const int n_end = CAUSAL ? min(S, m0 + BM3) : S;
+  k_st.issue(kp, 0, S, kv_tok);
+  v_st.issue(vtp, 0, S_pad);
+  k_st.write_rm(smem);
+  v_st.write(smem + KB);
+  __syncthreads();
+  int cur = 0;
+
+  for (int n0 = 0; n0 < n_end; n0 += BN) {
+    char* k_lds = smem + cur * (2 * KB);
+    char* vt_lds = k_lds + KB;
+    const bool more = n0 + BN < n_end;
+    if (more) {
+      k_st.issue(kp, n0 + BN, S, kv_tok);
+      v_st.issue(vtp, n0 + BN, S_pad);
+    }
+
+    const bool strip_live = !CAUSAL || (n0 <= m0w + 31);
+    if (strip_live) {
+      // S^T strips (two 32-kv subtiles x 32 q cols), raw (unscaled)
+      f32x16 st[2];
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) st[ks][r] = 0.f;
+      __builtin_amdgcn_s_setprio(1);
+      // the first 32-key half's fragments are all in flight before its
+      // MFMA chain; the second half's are read one per MFMA of the first
+      bf16x8v ka[2][QC];
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int c = 0; c < QC; ++c)
+          ka[ks][c] = read_bfrag<D * 2>(
+              k_lds, ks * 32 + (lane & 31), c * 16 + hi * 8);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int c = 0; c < QC; ++c)
+          st[ks] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              ka[ks][c], q_reg[c], st[ks], 0, 0, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, QC, 0);
+#pragma unroll
+      for (int c = 0; c < QC; ++c) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, QC, 0);
+      __builtin_amdgcn_s_setprio(0);
+
+      // mask (edge tiles only) + in-lane row max of the raw scores
+      const bool needs_mask = (n0 + BN > S) ||
+                              (CAUSAL && (n0 + BN - 1 > m0w));
+      if (needs_mask) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int kvg = n0 + ks * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            if ((CAUSAL && kvg > qrow) || kvg >= S || qrow >= S)
+              st[ks][r] = NEG_INF;
+          }
+      }
+      float mx = NEG_INF;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[ks][r]);
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * c2;
+      // defer-max (guide T13): when every row's max grew by < THR keep
+      // the old running max and skip the O rescale; P is then bounded by
+      // e^THR which the fp32 accumulator tolerates. Nothing of this tile
+      // is pending when the branch is taken (P*V of tile t completes
+      // before tile t+1's decision), so the T13 ordering hazard cannot
+      // occur in this structure. THR is 8 nats, in log2 units here.
+      constexpr float DEFER_THR = 8.f * LOG2E;
+      const bool rescale = !__all(mx <= m_run + DEFER_THR);
+      float alpha = 1.f;
+      if (rescale) {
+        const float mn = fmaxf(m_run, mx);
+        alpha = (m_run == NEG_INF) ? 0.f
+                                   : __builtin_amdgcn_exp2f(m_run - mn);
+        m_run = mn;
+      }
+      // a row with no live key so far: every score is -inf and must give
+      // p = 0, not exp2(-inf + inf)
+      const float neg_m = (m_run == NEG_INF) ? 0.f : -m_run;
+      float rsum = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float pe =
+              __builtin_amdgcn_exp2f(__builtin_fmaf(st[ks][r], c2, neg_m));
+          st[ks][r] = pe;
+          rsum += pe;
+        }
+      rsum += __shfl_xor(rsum, 32, 64);
+      l_run = l_run * alpha + rsum;
+
+      // rescale O by the per-ROW alpha (rows are reg-mapped; alpha is
+      // lane-mapped -> one bpermute gather per reg row); skipped
+      // entirely on the defer path
+      if (rescale) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int rowidx = (r & 3) + 8 * (r >> 2) + 4 * hi;
+          const float ar = __shfl(alpha, rowidx, 64);
+#pragma unroll
+          for (int t = 0; t < DT; ++t) o_acc[t][r] *= ar;
+        }
+      }
+
+      // P (f32, C-layout) -> bf16 A-fragments via cvt_pk + permlane swap
+      bf16x8v pa[4];
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+        repack_pa(st[ks], pa[2 * ks], pa[2 * ks + 1]);
+
+      // O += P * V
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int t = 0; t < DT; ++t) {
+          bf16x8v vb = read_bfrag<128>(
+              vt_lds, t * 32 + (lane & 31), ks * 16 + hi * 8);
+          o_acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              pa[ks], vb, o_acc[t], 0, 0, 0);
+        }
+      __builtin_amdgcn_s_setprio(0);
+    }
+    if (more) {
+      char* nk = smem + (cur ^ 1) * (2 * KB);
+      k_st.write_rm(nk);
+      v_st.write(nk + KB);
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  // epilogue. Every wave is past the loop's last barrier, so no K|V^T tile
+  // is read any more and each wave owns OWB bytes of smem. Within a wave
+  // LDS operations complete in program order.
+  char* ow = smem + wid * OWB;
+  if (hi == 0)
+    *(float*)(ow + (lane & 31) * 4) = (l_run > 0.f) ? 1.f / l_run : 0.f;
+  // 1/l of reg row r = 4g+j is row 8g + 4hi + j: four runs of four
+  f32x4 il[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+    il[g] = *(const f32x4*)(ow + (8 * g + 4 * hi) * 4);
+  __builtin_amdgcn_wave_barrier();
+  // O^T fragments -> row-major bf16 rows. The two half-waves write rows 4
+  // apart (same banks); XOR-ing byte 64 of the column with the row's bit 2
+  // (= hi) puts them on disjoint banks.
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int rowidx = (r & 3) + 8 * (r >> 2) + 4 * hi;
+#pragma unroll
+    for (int t = 0; t < DT; ++t) {
+      const int cb = (t * 32 + (lane & 31)) * 2;
+      *(bf16_t*)(ow + rowidx * (D * 2) + (cb ^ (hi << 6))) =
+          f2bf(o_acc[t][r] * il[r >> 2][r & 3]);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  constexpr int CPR = D * 2 / 16;   // 16-byte chunks per row
+  constexpr int RPI = WAVE / CPR;   // rows per wave-wide store
+#pragma unroll
+  for (int i = 0; i < 32 / RPI; ++i) {
+    const int row = i * RPI + lane / CPR;
+    const int ch = lane % CPR;
+    const uint4 val = *(const uint4*)(
+        ow + row * (D * 2) + ((ch * 16) ^ (((row >> 2) & 1) << 6)));
+    if (m0w + row < S)
+      *(uint4*)(op + (long)(m0w + row) * q_tok + ch * 8) = val;
+  }
+  if (hi == 0 && qrow < S)
+    lsep[qrow] = (l_run > 0.f) ? m_run * LN2 + __logf(l_run) : NEG_INF;
+}
+
+// ========================================================================
 // Backward preprocess: Dsum[b,h,m] = sum_d dO*O (fp32)
 // ========================================================================
 // grid (ceil(S/PRE_ROWS), Hq, B), 256 threads. A group of D/8 lanes
@@ -474,22 +762,6 @@ __global__ __launch_bounds__(256) void attn_bwd_pre_kernel(
 // registers as the MFMA B-operand; P^T / dS^T stay in-register and are
 // repacked with cvt_pk+permlane32_swap.
 // ========================================================================
-DEVINL void repack_pa(const f32x16& pt, bf16x8v& pa0, bf16x8v& pa1) {
-  union { uint32_t w[4]; bf16x8v f; } f0, f1;
-  auto sA = __builtin_amdgcn_permlane32_swap(
-      pack_bf16(pt[0], pt[1]), pack_bf16(pt[4], pt[5]), false, false);
-  auto sB = __builtin_amdgcn_permlane32_swap(
-      pack_bf16(pt[2], pt[3]), pack_bf16(pt[6], pt[7]), false, false);
-  f0.w[0] = sA[0]; f0.w[1] = sB[0]; f0.w[2] = sA[1]; f0.w[3] = sB[1];
-  auto sC = __builtin_amdgcn_permlane32_swap(
-      pack_bf16(pt[8], pt[9]), pack_bf16(pt[12], pt[13]), false, false);
-  auto sD = __builtin_amdgcn_permlane32_swap(
-      pack_bf16(pt[10], pt[11]), pack_bf16(pt[14], pt[15]), false, false);
-  f1.w[0] = sC[0]; f1.w[1] = sD[0]; f1.w[2] = sC[1]; f1.w[3] = sD[1];
-  pa0 = f0.f;
-  pa1 = f1.f;
-}
-
 template <int D, bool CAUSAL>
 __global__ __launch_bounds__(NTHREADS) void attn_bwd_dv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
@@ -1103,7 +1375,7 @@ __global__ __launch_bounds__(NTH_KV) void attn_bwd_dkdv_kernel(
       }
 
   const int m_start = CAUSAL ? n0 : 0;   // n0 is a multiple of QROWS
-  const float c2 = 1.4426950408889634f * scale;
+  const float c2 = LOG2E * scale;
   const long plane = (long)D * S_pad;
   const long head0 = (long)b * Hq + hkv * rep;
   const bf16_t* qh = q + ((long)b * S * q_tok) + (long)(hkv * rep) * D;
@@ -1227,6 +1499,10 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
   }
   const float lse_lane = (qrow < S) ? lsep[qrow] : NEG_INF;
   const float ds_lane = (qrow < S) ? dsp[qrow] : 0.f;
+  // p = exp(s*scale - lse) as exp2(fma(s, c2, nl2)): one fma + one v_exp
+  // per score. lse == -inf gives nl2 = +inf; those rows are masked below.
+  const float c2 = scale * LOG2E;
+  const float nl2 = -lse_lane * LOG2E;
 
   f32x16 dq_acc[DT];
 #pragma unroll
@@ -1288,7 +1564,7 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
                                (n0 + ks * 32 + 32 > S) || (m0w + 32 > S);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          float pv = __expf(sv[r] * scale - lse_lane);
+          float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sv[r], c2, nl2));
           if (need_mask) {
             const int kvg = n0 + ks * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
             if (!(qrow < S && kvg < S && (!CAUSAL || kvg <= qrow) &&
@@ -1299,25 +1575,7 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
         }
 
         bf16x8v da0, da1;
-        {
-          union { uint32_t w[4]; bf16x8v f; } f0, f1;
-          auto sA = __builtin_amdgcn_permlane32_swap(
-              pack_bf16(dst[0], dst[1]), pack_bf16(dst[4], dst[5]), false,
-              false);
-          auto sB = __builtin_amdgcn_permlane32_swap(
-              pack_bf16(dst[2], dst[3]), pack_bf16(dst[6], dst[7]), false,
-              false);
-          f0.w[0] = sA[0]; f0.w[1] = sB[0]; f0.w[2] = sA[1]; f0.w[3] = sB[1];
-          auto sC = __builtin_amdgcn_permlane32_swap(
-              pack_bf16(dst[8], dst[9]), pack_bf16(dst[12], dst[13]), false,
-              false);
-          auto sD = __builtin_amdgcn_permlane32_swap(
-              pack_bf16(dst[10], dst[11]), pack_bf16(dst[14], dst[15]),
-              false, false);
-          f1.w[0] = sC[0]; f1.w[1] = sD[0]; f1.w[2] = sC[1]; f1.w[3] = sD[1];
-          da0 = f0.f;
-          da1 = f1.f;
-        }
+        repack_pa(dst, da0, da1);
 #pragma unroll
         for (int t = 0; t < DT; ++t) {
           bf16x8v b0 = read_bfrag<128>(
@@ -1358,15 +1616,26 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
 extern "C" {
 
 // vt: pre-transposed V plane [B, Hkv, D, S_pad] (tok_transpose_head)
+// variant = 0: attn_fwd_kernel_v4 (default); variant = 1: the older v3,
+// kept so both can be timed and compared in one process.
 hipError_t tok_attn_fwd(const void* q, const void* k, const void* vt, void* o,
                         float* lse, int B, int S, int Hq, int Hkv, int D,
-                        int S_pad, int causal, hipStream_t stream) {
+                        int S_pad, int causal, hipStream_t stream,
+                        int variant) {
   dim3 grid((S + NW * 32 - 1) / (NW * 32), Hq, B);
   const float scale = 1.f / sqrtf((float)D);
+  if (variant != 0 && variant != 1) return hipErrorInvalidValue;
 #define LAUNCH_FWD(DD, CC)                                                    \
-  attn_fwd_kernel_v3<DD, CC><<<grid, NTHREADS, 0, stream>>>(                  \
-      (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)o,     \
-      lse, B, S, Hq, Hkv, S_pad, scale)
+  do {                                                                        \
+    if (variant == 1)                                                         \
+      attn_fwd_kernel_v3<DD, CC><<<grid, NTHREADS, 0, stream>>>(              \
+          (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)o, \
+          lse, B, S, Hq, Hkv, S_pad, scale);                                  \
+    else                                                                      \
+      attn_fwd_kernel_v4<DD, CC><<<grid, NTHREADS, 0, stream>>>(              \
+          (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)o, \
+          lse, B, S, Hq, Hkv, S_pad, scale);                                  \
+  } while (0)
   if (D == 128) { if (causal) LAUNCH_FWD(128, true); else LAUNCH_FWD(128, false); }
   else if (D == 64) { if (causal) LAUNCH_FWD(64, true); else LAUNCH_FWD(64, false); }
   else return hipErrorInvalidValue;

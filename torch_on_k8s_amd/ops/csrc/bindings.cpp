@@ -59,7 +59,8 @@ hipError_t tok_mfma_probe_32x32x16(const void* A, const void* B, float* D,
                                    hipStream_t stream);
 hipError_t tok_attn_fwd(const void* q, const void* k, const void* vt, void* o,
                         float* lse, int B, int S, int Hq, int Hkv, int D,
-                        int S_pad, int causal, hipStream_t stream);
+                        int S_pad, int causal, hipStream_t stream,
+                        int variant);
 hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
                         const void* o, const void* dout, const void* q_t,
                         const void* k_t, const void* dot_t, const float* lse,
@@ -344,8 +345,10 @@ void grad_norm_finalize_(at::Tensor partials, at::Tensor out, double inv_count,
 }
 
 // q: [B,S,Hq,D], k/v: [B,S,Hkv,D] bf16 contiguous -> (o, lse[B,Hq,S] f32)
+// variant = 0: the v4 forward kernel (default); 1: the older v3, for A/B
+// timing and cross-checks in one process.
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                 bool causal) {
+                                 bool causal, int64_t variant) {
   CHECK_BF16_CUDA(q);
   CHECK_BF16_CUDA(k);
   CHECK_BF16_CUDA(v);
@@ -354,6 +357,7 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
   TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
   TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == B && k.size(1) == S);
+  TORCH_CHECK(variant == 0 || variant == 1, "attn_fwd variant must be 0 or 1");
   auto o = at::empty_like(q);
   auto lse = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
   const int S_pad = (S + 63) / 64 * 64;
@@ -362,7 +366,8 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                 S_pad, current_stream()));
   TOK_HIP_OK(tok_attn_fwd(q.data_ptr(), k.data_ptr(), vt.data_ptr(),
                           o.data_ptr(), lse.data_ptr<float>(), B, S, Hq, Hkv,
-                          D, S_pad, causal ? 1 : 0, current_stream()));
+                          D, S_pad, causal ? 1 : 0, current_stream(),
+                          (int)variant));
   return {o, lse};
 }
 
@@ -510,7 +515,9 @@ at::Tensor mfma_probe(at::Tensor A, at::Tensor B) {
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("mfma_probe", &mfma_probe, "MFMA 16x16x32 bf16 layout probe");
-  mod.def("attn_fwd", &attn_fwd, "Flash attention forward (bf16, gfx950)");
+  mod.def("attn_fwd", &attn_fwd, "Flash attention forward (bf16, gfx950)",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
+          py::arg("variant") = 0);
   mod.def("attn_bwd", &attn_bwd, "Flash attention backward (bf16, gfx950)",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
           py::arg("lse"), py::arg("dout"), py::arg("causal"),
