@@ -4,7 +4,11 @@
 Measures fwd / bwd wall time and effective TFLOP/s of the gfx950 flash
 attention at the flagship shape, A/B against torch SDPA. The forward is
 timed both ways, v4 (default) and the older v3, and so is the backward,
-fused dK+dV (default) and split dV / dK, side by side.
+fused dK+dV (default) and split dV / dK, side by side; the fused backward
+is also timed with each dQ kernel (dq_variant 1 = 8-wave kernel in
+XCD-aware block order, the default; 0 = 4-wave kernel; 2 = 8-wave kernel in
+plain block order): the calls differ only in the dQ kernel, so the
+difference of their times is the difference of the dQ kernels.
 Within-process interleaved rounds (guide §5.4 rule 24). The flagship
 per-layer shape is --B 8; record runs at both --B 2 and --B 8.
 """
@@ -45,6 +49,8 @@ def main():
     ap.add_argument("--D", type=int, default=128)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--dq-variants", default="1,0,2",
+                    help="dQ kernels to time in the fused backward")
     ap.add_argument("--no-sdpa", action="store_true",
                     help="skip the torch SDPA columns (saves time at B=8)")
     args = ap.parse_args()
@@ -81,6 +87,12 @@ def main():
     def hip_bwd_split():   # older split dV / dK kernels
         return ops._C.attn_bwd(q, k, v, o_, lse_, do, True, True)
 
+    dq_variants = [int(x) for x in args.dq_variants.split(",")]
+
+    def hip_bwd_dq(variant):   # fused dK+dV with the given dQ kernel
+        return lambda: ops._C.attn_bwd(q, k, v, o_, lse_, do, True, False,
+                                       variant)
+
     qs = qt.detach().requires_grad_(True)
     ks = kt.detach().requires_grad_(True)
     vs = vt.detach().requires_grad_(True)
@@ -100,6 +112,12 @@ def main():
         th_f3 = time_fn(hip_fwd_v3, args.iters)
         th_b = time_fn(hip_bwd, args.iters)
         th_bs = time_fn(hip_bwd_split, args.iters)
+        th_dq = [time_fn(hip_bwd_dq(x), args.iters) for x in dq_variants]
+        print(f"[round {r}] hip bwd fused by dq_variant: " + " | ".join(
+            f"{x}: {t*1e3:7.3f} ms {fbw/t/1e12:6.1f} TF"
+            for x, t in zip(dq_variants, th_dq))
+            + f" | {dq_variants[-1]} - {dq_variants[0]}: "
+            f"{(th_dq[-1] - th_dq[0])*1e3:+.3f} ms", flush=True)
         if args.no_sdpa:
             print(f"[round {r}] hip fwd {th_f*1e3:7.2f} ms "
                   f"{ffw/th_f/1e12:7.1f} TF"
@@ -125,6 +143,13 @@ def main():
     print(f"max |O v4 - O v3| = "
           f"{(o_.float() - o3.float()).abs().max().item():.5f}, "
           f"max |LSE v4 - LSE v3| = {(lse_ - lse3).abs().max().item():.3e}")
+
+    # the dQ kernels against each other
+    dq0 = hip_bwd_dq(dq_variants[0])()[0]
+    for x in dq_variants[1:]:
+        dqx = hip_bwd_dq(x)()[0]
+        print(f"max |dQ variant {dq_variants[0]} - dQ variant {x}| = "
+              f"{(dq0.float() - dqx.float()).abs().max().item():.3e}")
 
     # correctness spot-check vs sdpa
     o_ref = sdpa_fwd().transpose(1, 2)

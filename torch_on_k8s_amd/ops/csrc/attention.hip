@@ -27,8 +27,11 @@
 //    in 256 accumulator registers, row constants as the accumulators'
 //    start values) and a deterministic dQ kernel over q tiles. The older
 //    split dV / dK pair (2 waves/SIMD, S recomputed in each) stays behind
-//    tok_attn_bwd's `split` selector for A/B timing. All kernels: 0
-//    scratch spill.
+//    tok_attn_bwd's `split` selector for A/B timing, and a 4-wave dQ
+//    kernel (64 q rows per wave, measured slower) behind `dq_variant`.
+//    All kernels: 0 scratch spill.
+//  * fwd v4, fused dK+dV and dQ take their block from xcd_block_index():
+//    the blocks that share a kv head's tiles run on one XCD's L2.
 //
 // Measured (B=2 S=4096 Hq=32 Hkv=8 D=128 causal, random data): fwd v3
 // 358-371 TF (parity with torch's aotriton flash), v4 see
@@ -62,6 +65,26 @@ DEVINL bf16x8v as_frag(uint4 raw) {
   union { uint4 u; bf16x8v f; } c;
   c.u = raw;
   return c.f;
+}
+
+// XCD-aware block order. Workgroups go to the 8 XCDs round-robin by linear
+// id, so the blocks that share one kv head's tiles (the q blocks and q
+// heads of a kv head in fwd / dQ, the key blocks of a kv head in dK+dV)
+// land on eight different L2s, and each of them fetches those tiles again.
+// Remapped, XCD r works through the r-th contiguous eighth of the grid: the
+// blocks in flight on one XCD share one or two kv heads. Measured on the
+// dQ kernel at B=8 S=4096: whole backward 8.91 -> 7.70 ms
+// (profiles/attn_dq_v2.log). Needs a block count divisible by 8; identity
+// otherwise. Which block computes what changes, no result does.
+DEVINL void xcd_block_index(int& bx, int& by, int& bz) {
+  const unsigned nx = gridDim.x, ny = gridDim.y;
+  const unsigned n = nx * ny * gridDim.z;
+  unsigned l = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
+  if (n % 8 == 0) l = (l % 8) * (n / 8) + l / 8;
+  bx = l % nx;
+  l /= nx;
+  by = l % ny;
+  bz = l / ny;
 }
 
 // ---- two-phase tile staging (async-STAGE split) -----------------------
@@ -456,10 +479,10 @@ __global__ __launch_bounds__(NTHREADS) void attn_fwd_kernel_v4(
   const int lane = threadIdx.x & 63;
   const int hi = lane >> 5;
   const int wid = threadIdx.x >> 6;
-  const int m0 = blockIdx.x * BM3;
+  int bx, hq, b;
+  xcd_block_index(bx, hq, b);
+  const int m0 = bx * BM3;
   const int m0w = m0 + wid * 32;
-  const int hq = blockIdx.y;
-  const int b = blockIdx.z;
   const int hkv = hq / (Hq / Hkv);
 
   const long q_tok = (long)Hq * D, kv_tok = (long)Hkv * D;
@@ -1329,10 +1352,10 @@ __global__ __launch_bounds__(NTH_KV) void attn_bwd_dkdv_kernel(
   const int lane = threadIdx.x & 63;
   const int hi = lane >> 5;
   const int wid = threadIdx.x >> 6;
-  const int n0 = blockIdx.x * BNK;
+  int bx, hkv, b;
+  xcd_block_index(bx, hkv, b);
+  const int n0 = bx * BNK;
   const int n0w = n0 + wid * 64;
-  const int hkv = blockIdx.y;
-  const int b = blockIdx.z;
   const int rep = Hq / Hkv;
 
   const long q_tok = (long)Hq * D, kv_tok = (long)Hkv * D;
@@ -1448,7 +1471,7 @@ __global__ __launch_bounds__(NTH_KV) void attn_bwd_dkdv_kernel(
 // Backward dQ v3: grid (ceil(S/256), Hq, B); 8 waves, wave = 32 q rows.
 // Q/dO in registers (lane owns q row); lse/Dsum are per-lane scalars.
 // ========================================================================
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, bool XCD>
 __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
@@ -1468,11 +1491,10 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
   // causal: the last q block has the most kv tiles; dispatch it first so
   // the grid does not end on a tail of 16-tile blocks (measured -3 % on
   // the whole backward, docs/ROADMAP.md)
-  const int m0 =
-      (CAUSAL ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x) * BM3;
+  int bx = blockIdx.x, hq = blockIdx.y, b = blockIdx.z;
+  if (XCD) xcd_block_index(bx, hq, b);
+  const int m0 = (CAUSAL ? (int)(gridDim.x - 1 - bx) : bx) * BM3;
   const int m0w = m0 + wid * 32;
-  const int hq = blockIdx.y;
-  const int b = blockIdx.z;
   const int hkv = hq / (Hq / Hkv);
 
   const long q_tok = (long)Hq * D, kv_tok = (long)Hkv * D;
@@ -1611,6 +1633,365 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
   }
 }
 
+// ========================================================================
+// Backward dQ v2: grid (ceil(S/256), Hq, B); 4 waves at 1 wave/SIMD, a
+// wave owns 64 q rows as two 32-row halves.
+//
+// Same arithmetic as attn_bwd_dq_kernel (element formula, key order of
+// every sum), restructured the way the fused dK+dV kernel was:
+//  * Q and dO of both halves stay in registers; every K, V and K^T
+//    fragment read from LDS feeds one MFMA per half: half the LDS read
+//    traffic per MFMA and two independent accumulator chains in place of
+//    the second wave per SIMD.
+//  * Reads run ahead of the chains: every fragment is read two chain
+//    steps (4-8 MFMAs) before the MFMAs that take it, the second
+//    subtile's first ones under the first subtile's last dQ MFMAs
+//    (sched_group_barrier), so the waits in front of the MFMAs are
+//    counted. Reading whole chains' fragments ahead spilled at D = 128.
+//  * The (K | K^T | V) tile is staged one tile ahead by global -> LDS DMA
+//    with the swizzle on the source side (see DkdvStage); key rows past S
+//    re-read row S-1, their p is 0 through the kvg < S mask, and the K^T
+//    plane's pad columns are zero (transpose.hip).
+//  * On the diagonal tile the second 32-key subtile lies entirely above
+//    the lower half's rows: only the upper half is computed (H0 = 1).
+//  * dQ leaves through the block's own LDS as 16-byte row pieces.
+// ========================================================================
+template <int D>
+struct DqStage {
+  static constexpr int NV = D / 32;                 // vecs/thread/image
+  static constexpr int KB = BN * D * 2;             // bytes per image
+  static constexpr int RM_STEP = NTH_KV * 16 / (D * 2);   // key rows
+  static constexpr int T_STEP = NTH_KV * 16 / 128;        // d rows
+  static_assert(RM_STEP % 16 == 0 && T_STEP % 16 == 0, "swizzle period");
+  static_assert(NV * RM_STEP == BN && NV * T_STEP == D, "image coverage");
+  int row_rm, col_rm, off_t;
+
+  DEVINL void init(int S_pad) {
+    const int o = threadIdx.x * 16;
+    int r, bb;
+    unswz(o, D * 2, r, bb);
+    row_rm = r;
+    col_rm = bb >> 1;
+    unswz(o, 128, r, bb);
+    off_t = r * S_pad + (bb >> 1);
+  }
+
+  // pointers at the (b, hkv) head; st = destination buffer (K | K^T | V).
+  // n0 + 64 <= S_pad, so the K^T columns are always inside the plane.
+  DEVINL void issue(const bf16_t* kp, const bf16_t* vp, const bf16_t* ktp,
+                    int n0, int S, long kv_tok, int S_pad, char* st) {
+    // the source offsets are recomputed per tile from these three: hoisted
+    // out of the tile loop they would hold ~20 registers across it
+    int rr = row_rm, cr = col_rm, ot = off_t;
+    asm volatile("" : "+v"(rr), "+v"(cr), "+v"(ot));
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      char* dst = st + (i * NTH_KV + (threadIdx.x & ~63)) * 16;
+      const long go = (long)min(n0 + rr + i * RM_STEP, S - 1) * kv_tok + cr;
+      const long to = (long)ot + (long)i * T_STEP * S_pad + n0;
+      glds<16>(kp + go, dst);
+      glds<16>(ktp + to, dst + KB);
+      glds<16>(vp + go, dst + 2 * KB);
+    }
+  }
+
+  DEVINL void finish() const {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+};
+
+// Per-lane row constants of one 32-row half (the lane owns row qrow).
+struct DqRow {
+  int qrow;
+  bool ok;        // qrow < S and lse finite
+  float nl2, ds;  // -lse*log2(e), Dsum
+};
+
+// dS^T of one 32-key subtile for one half, as the dQ product's A-fragments.
+template <bool CAUSAL>
+DEVINL void dq_ds_frags(const f32x16& sv, const f32x16& dpv, const DqRow& rw,
+                        float c2, bool need_mask, int kv0, int S,
+                        bf16x8v& da0, bf16x8v& da1) {
+  f32x16 dst;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sv[r], c2, rw.nl2));
+    if (need_mask) {
+      const int kvg = kv0 + (r & 3) + 8 * (r >> 2);
+      if (!(rw.ok && kvg < S && (!CAUSAL || kvg <= rw.qrow))) pv = 0.f;
+    }
+    dst[r] = pv * (dpv[r] - rw.ds);
+  }
+  repack_pa(dst, da0, da1);
+}
+
+// One 32-key subtile (32 keys from row ks*32 of the tile at k_lds) against
+// the halves H0..1. The S and dP chains advance together, one K and one V
+// fragment per step feeding 2*NHL MFMAs; the dQ chain takes one K^T
+// fragment per step for NHL MFMAs. Every LDS read is issued AH steps
+// (S/dP) or 2*AH steps (dQ) ahead of its MFMAs, 4*AH MFMAs with both
+// halves live: the last S/dP steps read the first K^T fragments, and with
+// FIRST (the tile's first subtile) the last dQ steps read the next
+// subtile's first K/V fragments into ka/va. A subtile that is not FIRST
+// finds ka/va[0..AH) read on entry.
+template <int D, bool CAUSAL, int H0, bool FIRST, int AH>
+DEVINL void dq2_subtile(const char* k_lds, int ks,
+                        bf16x8v (&ka)[D / 16], bf16x8v (&va)[D / 16],
+                        const bf16x8v (&q_reg)[2][D / 16],
+                        const bf16x8v (&do_reg)[2][D / 16],
+                        f32x16 (&dq_acc)[2][D / 32], const DqRow (&rw)[2],
+                        int n0, int m0w, int S, int lane, int hi, float c2) {
+  constexpr int QC = D / 16;
+  constexpr int DT = D / 32;
+  constexpr int NHL = 2 - H0;   // live halves
+  constexpr int KB = DqStage<D>::KB;
+  constexpr int AHQ = 2 * AH;
+  static_assert(2 * DT == QC && AHQ <= QC, "one K^T fragment per dQ step");
+  const char* kt_lds = k_lds + KB;
+  const char* v_lds = k_lds + 2 * KB;
+  const int krow = ks * 32 + (lane & 31);
+  auto read_kb = [&](int e) {
+    return read_bfrag<128>(kt_lds, (e >> 1) * 32 + (lane & 31),
+                           ks * 32 + (e & 1) * 16 + hi * 8);
+  };
+
+  f32x16 sv[2], dpv[2];
+#pragma unroll
+  for (int h = H0; h < 2; ++h)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      sv[h][r] = 0.f;
+      dpv[h][r] = 0.f;
+    }
+  bf16x8v kb[QC];
+  __builtin_amdgcn_s_setprio(1);
+  if (FIRST) {
+#pragma unroll
+    for (int c = 0; c < AH; ++c) {
+      ka[c] = read_bfrag<D * 2>(k_lds, krow, c * 16 + hi * 8);
+      va[c] = read_bfrag<D * 2>(v_lds, krow, c * 16 + hi * 8);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < QC; ++c) {
+#pragma unroll
+    for (int h = H0; h < 2; ++h) {
+      sv[h] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          ka[c], q_reg[h][c], sv[h], 0, 0, 0);
+      dpv[h] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          va[c], do_reg[h][c], dpv[h], 0, 0, 0);
+    }
+    if (c + AH < QC) {
+      ka[c + AH] = read_bfrag<D * 2>(k_lds, krow, (c + AH) * 16 + hi * 8);
+      va[c + AH] = read_bfrag<D * 2>(v_lds, krow, (c + AH) * 16 + hi * 8);
+    } else {
+      const int e = 2 * (c + AH - QC);
+      kb[e] = read_kb(e);
+      kb[e + 1] = read_kb(e + 1);
+    }
+  }
+  if (FIRST) __builtin_amdgcn_sched_group_barrier(0x100, 2 * AH, 0);
+#pragma unroll
+  for (int c = 0; c < QC; ++c) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 2 * NHL, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+  }
+  __builtin_amdgcn_s_setprio(0);
+
+  bf16x8v da[2][2];
+#pragma unroll
+  for (int h = H0; h < 2; ++h) {
+    const int m0h = m0w + h * 32;
+    const int kvs = n0 + ks * 32;
+    const bool need_mask =
+        (CAUSAL && kvs + 32 > m0h) || (kvs + 32 > S) || (m0h + 32 > S);
+    dq_ds_frags<CAUSAL>(sv[h], dpv[h], rw[h], c2, need_mask, kvs + 4 * hi, S,
+                        da[h][0], da[h][1]);
+  }
+
+  __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int c = 0; c < QC; ++c) {
+#pragma unroll
+    for (int h = H0; h < 2; ++h)
+      dq_acc[h][c >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+          da[h][c & 1], kb[c], dq_acc[h][c >> 1], 0, 0, 0);
+    if (c + AHQ < QC) {
+      kb[c + AHQ] = read_kb(c + AHQ);
+    } else if (FIRST) {
+      const int e = c + AHQ - QC;
+      const int e2 = e >> 1;
+      if (e & 1)
+        va[e2] = read_bfrag<D * 2>(v_lds, krow + 32, e2 * 16 + hi * 8);
+      else
+        ka[e2] = read_bfrag<D * 2>(k_lds, krow + 32, e2 * 16 + hi * 8);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < (FIRST ? QC : QC - AHQ); ++c) {
+    __builtin_amdgcn_sched_group_barrier(0x008, NHL, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+  }
+  __builtin_amdgcn_s_setprio(0);
+}
+
+template <int D, bool CAUSAL, int AH>
+__global__ __launch_bounds__(NTH_KV) void attn_bwd_dq_kernel_v2(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+    const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
+    const bf16_t* __restrict__ k_t, const float* __restrict__ lse,
+    const float* __restrict__ dsum, bf16_t* __restrict__ dq, int B, int S,
+    int Hq, int Hkv, int S_pad, float scale) {
+  constexpr int QC = D / 16;
+  constexpr int DT = D / 32;
+  constexpr int BMQ = NW_KV * 64;   // 256 q rows per block
+  constexpr int STB = 3 * DqStage<D>::KB;
+  constexpr int OHB = 32 * D * 2;   // a half's dQ rows in the epilogue
+  static_assert(NW_KV * 2 * OHB <= 2 * STB, "dQ staging fits the buffers");
+  // double-buffered (K rm | KT | V rm): one barrier per kv tile
+  __shared__ __attribute__((aligned(16))) char smem[2 * STB];
+
+  const int lane = threadIdx.x & 63;
+  const int hi = lane >> 5;
+  const int wid = threadIdx.x >> 6;
+  // causal: heaviest q block first, as in attn_bwd_dq_kernel
+  int bx, hq, b;
+  xcd_block_index(bx, hq, b);
+  const int m0 = (CAUSAL ? (int)(gridDim.x - 1 - bx) : bx) * BMQ;
+  const int m0w = m0 + wid * 64;
+  const int hkv = hq / (Hq / Hkv);
+
+  const long q_tok = (long)Hq * D, kv_tok = (long)Hkv * D;
+  const bf16_t* qp = q + ((long)b * S * q_tok) + (long)hq * D;
+  const bf16_t* kp = k + ((long)b * S * kv_tok) + (long)hkv * D;
+  const bf16_t* vp = v + ((long)b * S * kv_tok) + (long)hkv * D;
+  const bf16_t* dop = dout + ((long)b * S * q_tok) + (long)hq * D;
+  const bf16_t* ktp = k_t + ((long)b * Hkv + hkv) * (long)D * S_pad;
+  const float* lsep = lse + ((long)b * Hq + hq) * S;
+  const float* dsp = dsum + ((long)b * Hq + hq) * S;
+  bf16_t* dqp = dq + ((long)b * S * q_tok) + (long)hq * D;
+
+  const int n_end = CAUSAL ? min(S, m0 + BMQ) : S;
+  DqStage<D> stg;
+  stg.init(S_pad);
+  stg.issue(kp, vp, ktp, 0, S, kv_tok, S_pad, smem);
+
+  bf16x8v q_reg[2][QC], do_reg[2][QC];
+  DqRow rw[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int qrow = m0w + h * 32 + (lane & 31);
+#pragma unroll
+    for (int c = 0; c < QC; ++c) {
+      uint4 qr = {0, 0, 0, 0}, dor = {0, 0, 0, 0};
+      if (qrow < S) {
+        qr = *(const uint4*)(qp + (long)qrow * q_tok + c * 16 + hi * 8);
+        dor = *(const uint4*)(dop + (long)qrow * q_tok + c * 16 + hi * 8);
+      }
+      q_reg[h][c] = as_frag(qr);
+      do_reg[h][c] = as_frag(dor);
+    }
+    const float lse_lane = (qrow < S) ? lsep[qrow] : NEG_INF;
+    rw[h].qrow = qrow;
+    rw[h].ok = qrow < S && lse_lane != NEG_INF;
+    // p = exp(s*scale - lse) as exp2(fma(s, c2, nl2)); lse == -inf gives
+    // nl2 = +inf, those rows are masked through ok
+    rw[h].nl2 = -lse_lane * LOG2E;
+    rw[h].ds = (qrow < S) ? dsp[qrow] : 0.f;
+  }
+  const float c2 = scale * LOG2E;
+
+  f32x16 dq_acc[2][DT];
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int t = 0; t < DT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dq_acc[h][t][r] = 0.f;
+
+  stg.finish();
+  __syncthreads();
+  int cur = 0;
+
+  for (int n0 = 0; n0 < n_end; n0 += BN) {
+    const char* k_lds = smem + cur * STB;
+    const bool more = n0 + BN < n_end;
+    // the other buffer was last read before the previous barrier
+    if (more)
+      stg.issue(kp, vp, ktp, n0 + BN, S, kv_tok, S_pad,
+                smem + (cur ^ 1) * STB);
+
+    // wave-uniform: the wave has rows, and the tile is not entirely above
+    // them (m0w and n0 are multiples of 64, so both halves agree)
+    const bool live = m0w < S && (!CAUSAL || n0 <= m0w);
+    if (live) {
+      // the LDS read addresses are cheap functions of the lane; hidden
+      // from loop-invariant hoisting they are recomputed per tile, hoisted
+      // they take ~40 registers across the loop (spills at D = 128)
+      int lane_t = lane;
+      asm volatile("" : "+v"(lane_t));
+      const int hi_t = lane_t >> 5;
+      bf16x8v ka[QC], va[QC];
+      dq2_subtile<D, CAUSAL, 0, true, AH>(k_lds, 0, ka, va, q_reg, do_reg,
+                                          dq_acc, rw, n0, m0w, S, lane_t,
+                                          hi_t, c2);
+      // diagonal tile: keys n0+32.. are all above the lower half's rows
+      if (CAUSAL && n0 == m0w)
+        dq2_subtile<D, CAUSAL, 1, false, AH>(k_lds, 1, ka, va, q_reg, do_reg,
+                                             dq_acc, rw, n0, m0w, S, lane_t,
+                                             hi_t, c2);
+      else
+        dq2_subtile<D, CAUSAL, 0, false, AH>(k_lds, 1, ka, va, q_reg, do_reg,
+                                             dq_acc, rw, n0, m0w, S, lane_t,
+                                             hi_t, c2);
+    }
+    if (more) stg.finish();
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  // epilogue. Every wave is past the loop's last barrier and no DMA is in
+  // flight, so the stage buffers are free and each wave owns 2*OHB bytes.
+  // O^T-style fragments -> row-major bf16 rows, then whole 16-byte pieces;
+  // the XOR of byte 64 with the row's bit 2 (= hi) keeps the two
+  // half-waves' 2-byte writes on disjoint banks (as in the v4 forward).
+  constexpr int CPR = D * 2 / 16;   // 16-byte chunks per row
+  constexpr int RPI = WAVE / CPR;   // rows per wave-wide store
+  // lane-derived epilogue addresses are recomputed here, not carried
+  // across the tile loop
+  int lane_e = lane;
+  asm volatile("" : "+v"(lane_e));
+  const int hi_e = lane_e >> 5;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    char* ow = smem + (wid * 2 + h) * OHB;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int rowidx = (r & 3) + 8 * (r >> 2) + 4 * hi_e;
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        const int cb = (t * 32 + (lane_e & 31)) * 2;
+        *(bf16_t*)(ow + rowidx * (D * 2) + (cb ^ (hi_e << 6))) =
+            f2bf(dq_acc[h][t][r] * scale);
+      }
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const char* ow = smem + (wid * 2 + h) * OHB;
+#pragma unroll
+    for (int i = 0; i < 32 / RPI; ++i) {
+      const int row = i * RPI + lane_e / CPR;
+      const int ch = lane_e % CPR;
+      const uint4 val = *(const uint4*)(
+          ow + row * (D * 2) + ((ch * 16) ^ (((row >> 2) & 1) << 6)));
+      if (m0w + h * 32 + row < S)
+        *(uint4*)(dqp + (long)(m0w + h * 32 + row) * q_tok + ch * 8) = val;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1646,14 +2027,20 @@ hipError_t tok_attn_fwd(const void* q, const void* k, const void* vt, void* o,
 // q_t/k_t/dot_t: pre-transposed [.., D, S_pad] planes (tok_transpose_head)
 // split = 0: pre -> fused dK+dV -> dQ (default); split = 1: pre -> dV ->
 // dK -> dQ with the 8-wave split kernels, kept so both paths can be timed
-// and compared in one process.
+// and compared in one process. dq_variant selects the dQ kernel the same
+// way: 1 = the 8-wave attn_bwd_dq_kernel in XCD-aware block order (the
+// default of the Python binding), 0 = the 4-wave attn_bwd_dq_kernel_v2
+// (same order; measured slower, see there), 2 = the 8-wave kernel in plain
+// block order, as it ran before the reordering.
 hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
                         const void* o, const void* dout, const void* q_t,
                         const void* k_t, const void* dot_t, const float* lse,
                         float* dsum_ws, float* rc_ws, void* dq, void* dk,
                         void* dv, int B, int S, int Hq, int Hkv, int D,
-                        int S_pad, int causal, hipStream_t stream, int split) {
+                        int S_pad, int causal, hipStream_t stream, int split,
+                        int dq_variant) {
   const float scale = 1.f / sqrtf((float)D);
+  if (dq_variant < 0 || dq_variant > 2) return hipErrorInvalidValue;
   dim3 gpre((S + PRE_ROWS - 1) / PRE_ROWS, Hq, B);
   if (D == 128)
     attn_bwd_pre_kernel<128><<<gpre, 256, 0, stream>>>(
@@ -1686,10 +2073,22 @@ hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
           (const bf16_t*)dout, (const bf16_t*)q_t, (const bf16_t*)dot_t,      \
           rc_ws, (bf16_t*)dk, (bf16_t*)dv, B, S, Hq, Hkv, S_pad, scale);      \
     }                                                                         \
-    attn_bwd_dq_kernel<DD, CC><<<gq, NTHREADS, 0, stream>>>(                  \
-        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,                 \
-        (const bf16_t*)dout, (const bf16_t*)k_t, lse, dsum_ws, (bf16_t*)dq,  \
-        B, S, Hq, Hkv, S_pad, scale);                                         \
+    if (dq_variant == 0)                                                      \
+      attn_bwd_dq_kernel_v2<DD, CC, (CC ? 2 : 1)>                             \
+          <<<gq, NTH_KV, 0, stream>>>(                                        \
+          (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,               \
+          (const bf16_t*)dout, (const bf16_t*)k_t, lse, dsum_ws,              \
+          (bf16_t*)dq, B, S, Hq, Hkv, S_pad, scale);                          \
+    else if (dq_variant == 1)                                                 \
+      attn_bwd_dq_kernel<DD, CC, true><<<gq, NTHREADS, 0, stream>>>(          \
+          (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,               \
+          (const bf16_t*)dout, (const bf16_t*)k_t, lse, dsum_ws,              \
+          (bf16_t*)dq, B, S, Hq, Hkv, S_pad, scale);                          \
+    else                                                                      \
+      attn_bwd_dq_kernel<DD, CC, false><<<gq, NTHREADS, 0, stream>>>(         \
+          (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,               \
+          (const bf16_t*)dout, (const bf16_t*)k_t, lse, dsum_ws,              \
+          (bf16_t*)dq, B, S, Hq, Hkv, S_pad, scale);                          \
   } while (0)
   if (D == 128) { if (causal) LAUNCH_BWD(128, true); else LAUNCH_BWD(128, false); }
   else { if (causal) LAUNCH_BWD(64, true); else LAUNCH_BWD(64, false); }

@@ -66,7 +66,8 @@ hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
                         const void* k_t, const void* dot_t, const float* lse,
                         float* dsum_ws, float* rc_ws, void* dq, void* dk,
                         void* dv, int B, int S, int Hq, int Hkv, int D,
-                        int S_pad, int causal, hipStream_t stream, int split);
+                        int S_pad, int causal, hipStream_t stream, int split,
+                        int dq_variant);
 hipError_t tok_transpose_head(const void* in, void* out, int B, int S, int H,
                               int D, int S_pad, hipStream_t stream);
 hipError_t tok_attn_decode(const void* q, const void* k, const void* v,
@@ -373,13 +374,17 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
 
 // split = false: fused dK+dV kernel (default); true: the older split
 // dV / dK kernels, for A/B timing and cross-checks in one process.
+// dq_variant = 1: the 8-wave dQ kernel in XCD-aware block order (default);
+// 0: the 4-wave dQ kernel; 2: the 8-wave kernel in plain block order.
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor o, at::Tensor lse, at::Tensor dout,
-                                 bool causal, bool split) {
+                                 bool causal, bool split, int64_t dq_variant) {
   CHECK_BF16_CUDA(q);
   CHECK_BF16_CUDA(dout);
   const int B = q.size(0), S = q.size(1), Hq = q.size(2), D = q.size(3);
   const int Hkv = k.size(2);
+  TORCH_CHECK(dq_variant >= 0 && dq_variant <= 2,
+              "attn_bwd dq_variant must be 0, 1 or 2");
   auto dq = at::empty_like(q);
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
@@ -403,7 +408,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                           lse.data_ptr<float>(), dsum.data_ptr<float>(),
                           rc.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S,
                           Hq, Hkv, D, S_pad, causal ? 1 : 0, current_stream(),
-                          split ? 1 : 0));
+                          split ? 1 : 0, (int)dq_variant));
   return {dq, dk, dv};
 }
 
@@ -521,7 +526,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("attn_bwd", &attn_bwd, "Flash attention backward (bf16, gfx950)",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
           py::arg("lse"), py::arg("dout"), py::arg("causal"),
-          py::arg("split") = false);
+          py::arg("split") = false, py::arg("dq_variant") = 1);
   mod.def("ce_fwd", &ce_fwd, "Fused cross-entropy forward (bf16, gfx950)");
   mod.def("layernorm_fwd", &layernorm_fwd, "LayerNorm forward (bf16, gfx950)");
   mod.def("attn_decode", &attn_decode,
