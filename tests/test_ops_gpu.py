@@ -6,6 +6,7 @@ reference of the same op (tolerances account for bf16 I/O).
 import pytest
 import torch
 
+import kernel_oracle as ko
 from torch_on_k8s_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -88,32 +89,52 @@ def test_rope_fwd_bwd():
     assert (xg.grad.float().cpu() - dx_ref.float()).abs().max() < 0.03
 
 
-def test_fused_adamw_vs_reference():
-    torch.manual_seed(0)
-    n = 4096 + 8
-    p0 = torch.randn(n)
-    g = torch.randn(n)
-
-    # CPU fp32 reference (itself verified vs torch.optim.AdamW on CPU)
-    p_ref = p0.clone()
-    m_ref = torch.zeros(n)
-    v_ref = torch.zeros(n)
-    for step in range(1, 5):
-        ops.fused_adamw_(p_ref, g, m_ref, v_ref, lr=1e-2, beta1=0.9,
-                         beta2=0.95, eps=1e-8, weight_decay=0.1, step=step,
-                         grad_scale=0.5)
-
-    pg = p0.bfloat16().to(dev())
-    gg = g.bfloat16().to(dev())
+def _adamw_steps_vs_fp64(n, weight_decay, steps=3, tail=0):
+    """Every step is judged on its own, from the state the kernel left:
+    p (bf16) by the bf16 rule, m and v (fp32) by the fp32 rule of
+    kernel_oracle.py. A trajectory compared only at its end would have to
+    forgive a whole bf16 ulp wherever one rounding fell the other way."""
+    hp = dict(lr=1e-3, beta1=0.9, beta2=0.95, eps=1e-8,
+              weight_decay=weight_decay, grad_scale=0.5)
+    gen = torch.Generator().manual_seed(0)
+    p0 = ko.q16(0.02 * torch.randn(n, generator=gen))
+    g = ko.q16(torch.randn(n, generator=gen))
+    pg, gg = p0.to(dev()), g.to(dev())
     mg = torch.zeros(n, device=dev())
     vg = torch.zeros(n, device=dev())
-    for step in range(1, 5):
-        ops.fused_adamw_(pg, gg, mg, vg, lr=1e-2, beta1=0.9, beta2=0.95,
-                         eps=1e-8, weight_decay=0.1, step=step, grad_scale=0.5)
+    for step in range(1, steps + 1):
+        specs = ko.adamw_step(pg, g, mg, vg, step=step, **hp)
+        before = pg.clone()
+        ops.fused_adamw_(pg, gg, mg, vg, step=step, **hp)
+        got = {"p": pg, "m": mg, "v": vg}
+        tag = f"adamw[n={n},wd={weight_decay},t={step}]"
+        ko.check_all(tag, got, specs)
+        if tail:  # the elements only a later grid sweep reaches
+            ko.check_all(tag + ".tail", {k: t[-tail:] for k, t in got.items()},
+                         {k: ko.Spec(s.ref[-tail:], s.scale[-tail:], s.k,
+                                     s.bf16) for k, s in specs.items()})
+            assert (pg[-tail:] != before[-tail:]).all()
+        # a kernel that never writes p must not pass
+        assert (pg != before).all(), "some p elements did not move"
+    assert (pg.cpu() != p0).all()
+    assert (mg != 0).all() and (vg > 0).all()
 
-    assert (pg.float().cpu() - p_ref).abs().max() < 0.05
-    assert (mg.cpu() - m_ref).abs().max() < 0.02
-    assert (vg.cpu() - v_ref).abs().max() < 0.02
+
+def test_fused_adamw_vs_reference():
+    # wd = 0.1 is the trainer's; at wd = 8, lr*wd exceeds a bf16 half ulp,
+    # so a kernel without the decay term cannot pass either
+    _adamw_steps_vs_fp64(4096 + 8, 0.1)
+    _adamw_steps_vs_fp64(4096 + 8, 8.0)
+
+
+def test_fused_adamw_single_vector():
+    _adamw_steps_vs_fp64(8, 0.1)
+
+
+def test_fused_adamw_second_grid_sweep():
+    """2048 blocks x 256 threads x 8 elements = 4,194,304 per sweep; the
+    8000 elements beyond exist only for the stride loop."""
+    _adamw_steps_vs_fp64(4_194_304 + 8000, 0.1, tail=8000)
 
 
 def test_fused_cross_entropy():

@@ -112,9 +112,10 @@ class _RMSNormResFn(torch.autograd.Function):
             H = xr.shape[-1]
             r = invr.view(*xr.shape[:-1], 1)
             c = (dyf * wf * xf).sum(-1, keepdim=True)
-            dx = (r * (wf * dyf - xf * (r * r / H) * c)).to(xr.dtype)
-            if dxr is not None:
-                dx = dx + dxr
+            dx = r * (wf * dyf - xf * (r * r / H) * c)
+            if dxr is not None:  # added in fp32, one rounding, as the kernel
+                dx = dx + dxr.float()
+            dx = dx.to(xr.dtype)
             dw = (dyf * xf * r).reshape(-1, H).sum(0)
         dres = dx if ctx.has_res else None
         return dx, dres, dw.to(w.dtype), None
@@ -133,12 +134,15 @@ def rmsnorm_residual(x: torch.Tensor, res: torch.Tensor | None,
 # --------------------------------------------------------------------------
 def rope_ref(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
              sign: float = 1.0) -> torch.Tensor:
-    """x: [B, S, H, D]; cos/sin: [S, D/2] fp32."""
+    """x: [B, S, H, D]; cos/sin: [>= S, D/2] fp32, row s = position s."""
     B, S, H, D = x.shape
+    if cos.shape[0] < S or sin.shape[0] < S:
+        raise ValueError(
+            f"rope table has {cos.shape[0]} rows, sequence needs {S}")
     xf = x.float()
     x1, x2 = xf[..., : D // 2], xf[..., D // 2:]
-    cs = cos.view(1, S, 1, D // 2)
-    sn = sin.view(1, S, 1, D // 2) * sign
+    cs = cos[:S].reshape(1, S, 1, D // 2)
+    sn = sin[:S].reshape(1, S, 1, D // 2) * sign
     return torch.cat([x1 * cs - x2 * sn, x2 * cs + x1 * sn], dim=-1).to(x.dtype)
 
 

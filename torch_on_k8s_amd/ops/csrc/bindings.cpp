@@ -32,15 +32,15 @@ hipError_t tok_swiglu_bwd(const void* dout, const void* gu, void* dgu,
 hipError_t tok_qkv_rope_fwd(const void* qkv, void* q, void* k, void* v,
                             const float* cos_tab, const float* sin_tab,
                             long tokens, int Hq, int Hkv, int D,
-                            long table_rows, hipStream_t stream);
+                            long S, hipStream_t stream);
 hipError_t tok_qkv_rope_bwd(const void* dq, const void* dk, const void* dv,
                             void* dqkv, const float* cos_tab,
                             const float* sin_tab, long tokens, int Hq,
-                            int Hkv, int D, long table_rows,
+                            int Hkv, int D, long S,
                             hipStream_t stream);
 hipError_t tok_rope(const void* x, void* y, const float* cos_tab,
                     const float* sin_tab, long rows_total, int heads, int D,
-                    long table_rows, float sign, hipStream_t stream);
+                    long S, float sign, hipStream_t stream);
 hipError_t tok_adamw(void* p, const void* g, float* m, float* v, long n,
                      float lr, float beta1, float beta2, float eps, float wd,
                      int step, float gscale, const int* step_dev,
@@ -139,6 +139,10 @@ std::vector<at::Tensor> rmsnorm_bwd(at::Tensor x, at::Tensor w, at::Tensor dy,
   return {dx, dw};
 }
 
+// The fused residual kernels keep a row in registers, at most 8 vectors of
+// 8 per thread of a 256-thread block: wider rows have no kernel.
+constexpr long kRmsnormResMaxH = 8 * 256 * 8;
+
 // Fused residual + RMSNorm: (x, res?, w) -> (y, xr, invr)
 std::vector<at::Tensor> rmsnorm_res_fwd(at::Tensor x,
                                         c10::optional<at::Tensor> res,
@@ -147,6 +151,9 @@ std::vector<at::Tensor> rmsnorm_res_fwd(at::Tensor x,
   CHECK_BF16_CUDA(w);
   const long H = x.size(-1);
   TORCH_CHECK(H % 8 == 0, "hidden dim must be a multiple of 8");
+  TORCH_CHECK(H <= kRmsnormResMaxH, "rmsnorm_res: hidden dim ", H,
+              " exceeds ", kRmsnormResMaxH);
+  TORCH_CHECK(w.numel() == H, "weight shape mismatch");
   const long nrows = x.numel() / H;
   const void* res_p = nullptr;
   if (res.has_value()) {
@@ -171,6 +178,9 @@ std::vector<at::Tensor> rmsnorm_res_bwd(at::Tensor xr, at::Tensor w,
   CHECK_BF16_CUDA(xr);
   CHECK_BF16_CUDA(dy);
   const long H = xr.size(-1);
+  TORCH_CHECK(H % 8 == 0, "hidden dim must be a multiple of 8");
+  TORCH_CHECK(H <= kRmsnormResMaxH, "rmsnorm_res: hidden dim ", H,
+              " exceeds ", kRmsnormResMaxH);
   const long nrows = xr.numel() / H;
   const void* dxr_p = nullptr;
   if (dxr.has_value()) {
@@ -228,16 +238,16 @@ std::vector<at::Tensor> qkv_rope_fwd(at::Tensor qkv, at::Tensor cos_tab,
   TORCH_CHECK(qkv.size(2) == (Hq + 2 * Hkv) * D, "packed qkv dim mismatch");
   const long tokens = B * S;
   const long table_rows = cos_tab.numel() / (D / 2);
-  TORCH_CHECK(S % table_rows == 0 || table_rows % S == 0 || table_rows == S,
-              "rope table rows must match sequence");
+  TORCH_CHECK(sin_tab.numel() == cos_tab.numel(), "cos/sin shape mismatch");
+  TORCH_CHECK(table_rows >= S, "rope table has ", table_rows,
+              " rows, sequence needs ", S);
   auto q = at::empty({B, S, Hq, D}, qkv.options());
   auto k = at::empty({B, S, Hkv, D}, qkv.options());
   auto v = at::empty({B, S, Hkv, D}, qkv.options());
   TOK_HIP_OK(tok_qkv_rope_fwd(qkv.data_ptr(), q.data_ptr(), k.data_ptr(),
                               v.data_ptr(), cos_tab.data_ptr<float>(),
                               sin_tab.data_ptr<float>(), tokens, (int)Hq,
-                              (int)Hkv, (int)D, table_rows,
-                              current_stream()));
+                              (int)Hkv, (int)D, S, current_stream()));
   return {q, k, v};
 }
 
@@ -249,13 +259,17 @@ at::Tensor qkv_rope_bwd(at::Tensor dq, at::Tensor dk, at::Tensor dv,
   const long B = dq.size(0), S = dq.size(1), Hq = dq.size(2), D = dq.size(3);
   const long Hkv = dk.size(2);
   const long tokens = B * S;
+  TORCH_CHECK(cos_tab.scalar_type() == at::kFloat && cos_tab.is_contiguous());
+  TORCH_CHECK(sin_tab.scalar_type() == at::kFloat && sin_tab.is_contiguous());
+  TORCH_CHECK(sin_tab.numel() == cos_tab.numel(), "cos/sin shape mismatch");
   const long table_rows = cos_tab.numel() / (D / 2);
+  TORCH_CHECK(table_rows >= S, "rope table has ", table_rows,
+              " rows, sequence needs ", S);
   auto dqkv = at::empty({B, S, (Hq + 2 * Hkv) * D}, dq.options());
   TOK_HIP_OK(tok_qkv_rope_bwd(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
                               dqkv.data_ptr(), cos_tab.data_ptr<float>(),
                               sin_tab.data_ptr<float>(), tokens, (int)Hq,
-                              (int)Hkv, (int)D, table_rows,
-                              current_stream()));
+                              (int)Hkv, (int)D, S, current_stream()));
   return dqkv;
 }
 
@@ -268,12 +282,16 @@ at::Tensor rope(at::Tensor x, at::Tensor cos_tab, at::Tensor sin_tab,
   TORCH_CHECK(D % 16 == 0, "head dim must be a multiple of 16");
   const long rows_total = x.numel() / D;
   const long table_rows = cos_tab.numel() / (D / 2);
-  TORCH_CHECK((rows_total / heads) % table_rows == 0,
-              "rope table rows must divide token count");
+  TORCH_CHECK(x.dim() >= 3 && x.size(-2) == heads,
+              "rope expects [..., S, heads, D]");
+  const long S = x.size(-3);
+  TORCH_CHECK(sin_tab.numel() == cos_tab.numel(), "cos/sin shape mismatch");
+  TORCH_CHECK(table_rows >= S, "rope table has ", table_rows,
+              " rows, sequence needs ", S);
   auto y = at::empty_like(x);
   TOK_HIP_OK(tok_rope(x.data_ptr(), y.data_ptr(), cos_tab.data_ptr<float>(),
                       sin_tab.data_ptr<float>(), rows_total, (int)heads,
-                      (int)D, table_rows, (float)sign, current_stream()));
+                      (int)D, S, (float)sign, current_stream()));
   return y;
 }
 

@@ -23,29 +23,43 @@ __global__ void ln_fwd_kernel(const bf16x8* __restrict__ x,
   const int H = hc * 8;
   for (long row = blockIdx.x; row < nrows; row += gridDim.x) {
     const bf16x8* xr = x + row * hc;
-    float s1 = 0.f, s2 = 0.f;
-    for (int c = threadIdx.x; c < hc; c += BLOCK) {
-      bf16x8 v = xr[c];
+    // Two passes: the mean first, then the variance about it. The
+    // one-pass E[x^2] - mu^2 cancels in fp32 once |mu| >> std (rstd off
+    // by a whole bf16 rounding at mu = 200, std = 1). Each thread keeps
+    // its first vector in registers, so up to H = 2048 the row is read
+    // from memory once; wider rows reread the rest from cache.
+    const int c0 = threadIdx.x;
+    bf16x8 v0 = {};
+    if (c0 < hc) v0 = xr[c0];
+    float s1 = 0.f;
+    for (int c = c0; c < hc; c += BLOCK) {
+      bf16x8 v = (c == c0) ? v0 : xr[c];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float f = bfbits2f(v.h[j]);
-        s1 += f;
-        s2 = fmaf(f, f, s2);
-      }
+      for (int j = 0; j < 8; ++j) s1 += bfbits2f(v.h[j]);
     }
     s1 = block_reduce_sum(s1, red);
-    __syncthreads();
-    s2 = block_reduce_sum(s2, red);
     const float mu = s1 / (float)H;
-    const float var = s2 / (float)H - mu * mu;
+    float s2 = 0.f;
+    for (int c = c0; c < hc; c += BLOCK) {
+      bf16x8 v = (c == c0) ? v0 : xr[c];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float d = bfbits2f(v.h[j]) - mu;
+        s2 = fmaf(d, d, s2);
+      }
+    }
+    __syncthreads();  // red[] reused
+    s2 = block_reduce_sum(s2, red);
+    const float var = s2 / (float)H;
     const float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
     if (threadIdx.x == 0) {
       mu_out[row] = mu;
       rstd_out[row] = rstd;
     }
     bf16x8* yr = y + row * hc;
-    for (int c = threadIdx.x; c < hc; c += BLOCK) {
-      bf16x8 xv = xr[c], wv = w[c], bv = b[c], ov;
+    for (int c = c0; c < hc; c += BLOCK) {
+      bf16x8 xv = (c == c0) ? v0 : xr[c];
+      bf16x8 wv = w[c], bv = b[c], ov;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float f = (bfbits2f(xv.h[j]) - mu) * rstd * bfbits2f(wv.h[j]) +

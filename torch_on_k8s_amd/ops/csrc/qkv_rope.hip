@@ -12,8 +12,9 @@
 // Backward is the exact mirror: read dq/dk/dv, inverse-rotate dq/dk
 // (sign = -1), write the packed dqkv the GEMM backward consumes.
 //
-// cos/sin: host-precomputed fp32 [table_rows, D/2] (no device trig —
-// guide: memory-bound op must not become VALU-bound).
+// cos/sin: host-precomputed fp32 [>= S, D/2] (no device trig — guide:
+// memory-bound op must not become VALU-bound). position = token % S; the
+// caller checks that the table has at least S rows.
 #include "common.h"
 
 namespace {
@@ -30,7 +31,7 @@ __global__ void qkv_rope_kernel(const bf16x8* __restrict__ qkv,
                                 const float* __restrict__ tab_cos,
                                 const float* __restrict__ tab_sin,
                                 long tokens, int Hq, int Hkv, int hv /* (D/2)/8 */,
-                                long table_rows, float sign) {
+                                long S, float sign) {
   const int heads_total = Hq + 2 * Hkv;
   const int dv8 = hv * 2;  // vecs per head (D/8)
   const long nwork = tokens * heads_total * hv;
@@ -56,7 +57,7 @@ __global__ void qkv_rope_kernel(const bf16x8* __restrict__ qkv,
       rot = false;
     }
     if (rot) {
-      const long pos = token % table_rows;
+      const long pos = token % S;
       const float* cosr = tab_cos + pos * (hv * 8);
       const float* sinr = tab_sin + pos * (hv * 8);
       bf16x8 o1, o2;
@@ -86,7 +87,7 @@ __global__ void qkv_rope_bwd_kernel(const bf16x8* __restrict__ dq,
                                     const float* __restrict__ tab_cos,
                                     const float* __restrict__ tab_sin,
                                     long tokens, int Hq, int Hkv, int hv,
-                                    long table_rows) {
+                                    long S) {
   const int heads_total = Hq + 2 * Hkv;
   const int dv8 = hv * 2;
   const long nwork = tokens * heads_total * hv;
@@ -112,7 +113,7 @@ __global__ void qkv_rope_bwd_kernel(const bf16x8* __restrict__ dq,
     bf16x8 x2 = src[c + hv];
     bf16x8* dst = dqkv + (token * heads_total + h) * dv8;
     if (rot) {
-      const long pos = token % table_rows;
+      const long pos = token % S;
       const float* cosr = tab_cos + pos * (hv * 8);
       const float* sinr = tab_sin + pos * (hv * 8);
       bf16x8 o1, o2;
@@ -141,7 +142,7 @@ extern "C" {
 hipError_t tok_qkv_rope_fwd(const void* qkv, void* q, void* k, void* v,
                             const float* cos_tab, const float* sin_tab,
                             long tokens, int Hq, int Hkv, int D,
-                            long table_rows, hipStream_t stream) {
+                            long S, hipStream_t stream) {
   const int hv = (D / 2) / 8;
   const long nwork = tokens * (long)(Hq + 2 * Hkv) * hv;
   long grid = (nwork + BLOCK - 1) / BLOCK;
@@ -149,14 +150,14 @@ hipError_t tok_qkv_rope_fwd(const void* qkv, void* q, void* k, void* v,
   if (grid < 1) grid = 1;
   qkv_rope_kernel<<<(int)grid, BLOCK, 0, stream>>>(
       (const bf16x8*)qkv, (bf16x8*)q, (bf16x8*)k, (bf16x8*)v, cos_tab,
-      sin_tab, tokens, Hq, Hkv, hv, table_rows, 1.0f);
+      sin_tab, tokens, Hq, Hkv, hv, S, 1.0f);
   return hipGetLastError();
 }
 
 hipError_t tok_qkv_rope_bwd(const void* dq, const void* dk, const void* dv,
                             void* dqkv, const float* cos_tab,
                             const float* sin_tab, long tokens, int Hq,
-                            int Hkv, int D, long table_rows,
+                            int Hkv, int D, long S,
                             hipStream_t stream) {
   const int hv = (D / 2) / 8;
   const long nwork = tokens * (long)(Hq + 2 * Hkv) * hv;
@@ -165,7 +166,7 @@ hipError_t tok_qkv_rope_bwd(const void* dq, const void* dk, const void* dv,
   if (grid < 1) grid = 1;
   qkv_rope_bwd_kernel<<<(int)grid, BLOCK, 0, stream>>>(
       (const bf16x8*)dq, (const bf16x8*)dk, (const bf16x8*)dv, (bf16x8*)dqkv,
-      cos_tab, sin_tab, tokens, Hq, Hkv, hv, table_rows);
+      cos_tab, sin_tab, tokens, Hq, Hkv, hv, S);
   return hipGetLastError();
 }
 }

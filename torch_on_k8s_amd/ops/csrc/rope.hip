@@ -18,16 +18,16 @@ constexpr int BLOCK = 256;
 // vec in the second half. rows_total = B*S*Hh, hv = (D/2)/8 vecs per half.
 __global__ void rope_kernel(const bf16x8* __restrict__ x,
                             bf16x8* __restrict__ y,
-                            const float* __restrict__ tab_cos,  // [table_rows, D/2]
-                            const float* __restrict__ tab_sin,  // [table_rows, D/2]
-                            long rows_total, int heads, int hv, long table_rows,
+                            const float* __restrict__ tab_cos,  // [>= S, D/2]
+                            const float* __restrict__ tab_sin,  // [>= S, D/2]
+                            long rows_total, int heads, int hv, long S,
                             float sign) {
   const long nwork = rows_total * hv;
   for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < nwork;
        i += (long)gridDim.x * BLOCK) {
     const long row = i / hv;            // (b*S + s)*Hh + h
     const int c = (int)(i - row * hv);  // vec index within half
-    const long pos = (row / heads) % table_rows;  // position within sequence
+    const long pos = (row / heads) % S;  // position within sequence
     const int D = hv * 16;              // full head dim
     const bf16x8* xr = x + row * (D / 8);
     bf16x8* yr = y + row * (D / 8);
@@ -54,11 +54,11 @@ __global__ void rope_kernel(const bf16x8* __restrict__ x,
 
 extern "C" {
 
-// x,y: bf16 [rows_total, D]; cos_tab/sin_tab: fp32 [table_rows, D/2];
-// position = (row/heads) % table_rows.
+// x,y: bf16 [rows_total, D]; cos_tab/sin_tab: fp32 [>= S, D/2] (the
+// caller checks the row count); position = (row/heads) % S.
 hipError_t tok_rope(const void* x, void* y, const float* cos_tab,
                     const float* sin_tab, long rows_total, int heads, int D,
-                    long table_rows, float sign, hipStream_t stream) {
+                    long S, float sign, hipStream_t stream) {
   const int hv = (D / 2) / 8;
   const long nwork = rows_total * hv;
   long grid = (nwork + BLOCK - 1) / BLOCK;
@@ -66,7 +66,7 @@ hipError_t tok_rope(const void* x, void* y, const float* cos_tab,
   if (grid < 1) grid = 1;
   rope_kernel<<<(int)grid, BLOCK, 0, stream>>>(
       (const bf16x8*)x, (bf16x8*)y, cos_tab, sin_tab, rows_total, heads, hv,
-      table_rows, sign);
+      S, sign);
   return hipGetLastError();
 }
 }
