@@ -169,3 +169,9 @@ class GPT2Model(nn.Module):
                 nxt = logits.argmax(-1, keepdim=True)
             out = torch.cat([out, nxt], dim=1)
         return out
+
+    def generate_ragged(self, prompts, *args, **kwargs):
+        raise NotImplementedError(
+            "GPT-2 has no ragged-batch generation: its learned positions "
+            "need a per-sequence position gather that is not built. Use "
+            "generate() with prompts of one length, or a Llama model.")

@@ -341,6 +341,123 @@ class LlamaModel(nn.Module):
                 tokens.append(token_buf.clone())
         return torch.cat([input_ids] + tokens, dim=1)
 
+    @torch.no_grad()
+    def generate_ragged(self, prompts, max_new_tokens: int = 32,
+                        eos_token_id: int | None = None,
+                        use_graph: bool | None = None,
+                        pad_token_id: int = 0) -> list[torch.Tensor]:
+        """Greedy generation for prompts of different lengths (each a 1-D
+        id tensor or a list of ids, length >= 1). Returns one 1-D tensor
+        per sequence: the prompt followed by its new tokens, ending at the
+        first eos_token_id (inclusive) if one is given and emitted.
+
+        Prefill right-pads to the longest prompt and runs the causal
+        flash-attention kernel: a valid row never sees a pad key, and the
+        pad rows' K/V land in cache rows >= len_b, which decode never
+        reads before it overwrites them. Decode keeps per-sequence
+        lengths on the device (ops.qkv_rope_append_ +
+        ops.attention_decode_ragged), so one captured step serves every
+        sequence whatever its length."""
+        cfg = self.cfg
+        dev = self.embed_tokens.weight.device
+        dtype = self.embed_tokens.weight.dtype
+        seqs = [torch.as_tensor(p, dtype=torch.long).reshape(-1).to(dev)
+                for p in prompts]
+        if not seqs or any(s.numel() < 1 for s in seqs):
+            raise ValueError("generate_ragged needs >= 1 prompt, each of "
+                             "length >= 1")
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        B = len(seqs)
+        lens0 = torch.tensor([s.numel() for s in seqs], device=dev)
+        S0 = int(max(s.numel() for s in seqs))
+        Tmax = S0 + max_new_tokens
+        Hkv, Hq, D = cfg.num_kv_heads, cfg.num_heads, cfg.head_dim
+        input_ids = torch.full((B, S0), pad_token_id, dtype=torch.long,
+                               device=dev)
+        for b, s in enumerate(seqs):
+            input_ids[b, :s.numel()] = s
+        kc = [torch.zeros(B, Tmax, Hkv, D, dtype=dtype, device=dev)
+              for _ in self.layers]
+        vc = [torch.zeros(B, Tmax, Hkv, D, dtype=dtype, device=dev)
+              for _ in self.layers]
+        cos, sin = build_rope_table(cfg, Tmax, dev)
+
+        # prefill over the padded rectangle
+        x = self.embed_tokens(input_ids)
+        cs0, sn0 = cos[:S0].contiguous(), sin[:S0].contiguous()
+        for i, blk in enumerate(self.layers):
+            q, k, v = blk.attn.project_qkv(blk.input_norm(x), cs0, sn0)
+            kc[i][:, :S0] = k
+            vc[i][:, :S0] = v
+            o = ops.attention(q, k, v, causal=True)
+            x = x + blk.attn.o_proj(o.reshape(B, S0, Hq * D))
+            x = x + blk.mlp(blk.post_attn_norm(x))
+        last = x[torch.arange(B, device=dev), lens0 - 1].unsqueeze(1)
+        first = self.lm_head(self.norm(last))[:, -1].argmax(-1, keepdim=True)
+
+        # Decode state, all on the device. token_buf holds the token to
+        # feed; it sits at position pos = lens - 1 and attends to lens rows.
+        # A finished sequence has pos = -1 (no cache write, zero q), a
+        # length that no longer grows and a buffer slot that stays at eos.
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        token_buf = first.clone()                           # [B, 1]
+        finished = (token_buf[:, 0] == eos)
+        lens = (lens0 + (~finished)).to(torch.int32)
+        pos = torch.where(finished, -1, lens0).to(torch.int32)
+        tokens = [token_buf.clone()]
+
+        def decode_step():
+            x = self.embed_tokens(token_buf)
+            for i, blk in enumerate(self.layers):
+                h = blk.input_norm(x)
+                qkv = blk.attn.qkv_proj(h).view(B, (Hq + 2 * Hkv) * D)
+                q = ops.qkv_rope_append_(qkv, cos, sin, pos, kc[i], vc[i],
+                                         Hq, Hkv, D)
+                o = ops.attention_decode_ragged(q, kc[i], vc[i], lens)
+                x = x + blk.attn.o_proj(o.view(B, 1, Hq * D))
+                x = x + blk.mlp(blk.post_attn_norm(x))
+            nxt = self.lm_head(self.norm(x))[:, -1].argmax(-1)
+            nxt = torch.where(finished, eos, nxt)
+            finished.logical_or_(nxt == eos)
+            token_buf.copy_(nxt.unsqueeze(1))  # self-feed the next replay
+            lens.add_((~finished).to(torch.int32))
+            pos.copy_(torch.where(finished, -1, lens - 1))
+
+        if use_graph is None:
+            use_graph = dev.type == "cuda" and max_new_tokens >= 8
+
+        if not use_graph:
+            for _ in range(max_new_tokens - 1):
+                decode_step()
+                tokens.append(token_buf.clone())
+        else:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            n_warm = min(2, max_new_tokens - 1)
+            with torch.cuda.stream(side):
+                for _ in range(n_warm):  # real steps (allocator warm-up)
+                    decode_step()
+                    tokens.append(token_buf.clone())
+            torch.cuda.current_stream().wait_stream(side)
+            if max_new_tokens - 1 > n_warm:
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    decode_step()        # capture only; not executed
+                for _ in range(max_new_tokens - 1 - n_warm):
+                    graph.replay()
+                    tokens.append(token_buf.clone())
+
+        new = torch.cat(tokens, dim=1).tolist()             # one host read
+        out = []
+        for b, s in enumerate(seqs):
+            row = new[b]
+            if eos_token_id is not None and eos in row:
+                row = row[:row.index(eos) + 1]
+            out.append(torch.cat([s, torch.tensor(row, dtype=torch.long,
+                                                  device=dev)]))
+        return out
+
     def num_params(self) -> int:
         seen, total = set(), 0
         for p in self.parameters():

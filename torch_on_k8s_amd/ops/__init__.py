@@ -430,6 +430,104 @@ def attention_decode(q: torch.Tensor, kcache: torch.Tensor,
 
 
 # --------------------------------------------------------------------------
+# Ragged-batch decode: per-sequence KV lengths on the device (no autograd)
+# --------------------------------------------------------------------------
+_RAGGED_TARGET_BLOCKS = 512    # about two blocks per CU (256 CUs)
+_RAGGED_MIN_CHUNK = 64         # keys: one block step (4 loads x 16 rows)
+_RAGGED_MAX_CHUNK = 2048       # keys: a longer chunk is a long serial tail
+_RAGGED_MAX_SPLITS = 32
+_RAGGED_CHUNK_ALIGN = 16       # rows of one block step at D = 128
+
+
+def decode_ragged_splits(B: int, Hkv: int, Tmax: int) -> int:
+    """Default split count of attention_decode_ragged. Depends on shapes
+    alone — never on the lengths — so a captured grid stays valid. From the
+    sweep in profiles/decode_ragged.log: about two blocks per CU, but no
+    chunk above 2048 keys however many blocks that makes (unequal lengths
+    leave the long sequences' blocks running alone); no chunk below 64
+    keys; at most 32 splits."""
+    want = max(_RAGGED_TARGET_BLOCKS // max(1, B * Hkv),
+               -(-Tmax // _RAGGED_MAX_CHUNK))
+    return max(1, min(want, Tmax // _RAGGED_MIN_CHUNK, _RAGGED_MAX_SPLITS))
+
+
+def decode_ragged_chunk(Tmax: int, num_splits: int) -> int:
+    """Keys per split: split z owns rows [z*chunk, (z+1)*chunk)."""
+    per = -(-Tmax // max(1, num_splits))
+    return -(-per // _RAGGED_CHUNK_ALIGN) * _RAGGED_CHUNK_ALIGN
+
+
+@torch.no_grad()
+def attention_decode_ragged(q: torch.Tensor, kcache: torch.Tensor,
+                            vcache: torch.Tensor, lens: torch.Tensor, *,
+                            num_splits: int | None = None) -> torch.Tensor:
+    """q: [B, Hq, D] new-token queries (post-RoPE); kcache/vcache:
+    [B, Tmax, Hkv, D]; lens: [B] int32 on q's device. Sequence b attends to
+    rows [0, clamp(lens[b], 0, Tmax)); lens[b] == 0 gives a zero row. The
+    host never reads lens, so the call can be captured and a replay follows
+    new contents. Returns [B, Hq, D]."""
+    B, Hq, D = q.shape
+    Tmax, Hkv = kcache.shape[1], kcache.shape[2]
+    if num_splits is None:
+        num_splits = decode_ragged_splits(B, Hkv, Tmax)
+    if q.is_cuda:
+        return _require_ext("attention_decode_ragged").attn_decode_ragged(
+            q.contiguous(), kcache, vcache, lens, int(num_splits),
+            decode_ragged_chunk(Tmax, num_splits))
+    rep = Hq // Hkv
+    n = lens.clamp(0, Tmax).view(B, 1, 1)
+    dead = torch.arange(Tmax).view(1, 1, Tmax) >= n          # [B,1,Tmax]
+    # rows a sequence must not read may hold anything, NaN included
+    gone = dead.view(B, Tmax, 1, 1)
+    kf = kcache.float().masked_fill(gone, 0.0)
+    vf = vcache.float().masked_fill(gone, 0.0)
+    kf = kf.permute(0, 2, 1, 3).repeat_interleave(rep, 1)
+    vf = vf.permute(0, 2, 1, 3).repeat_interleave(rep, 1)
+    s = torch.einsum("bhd,bhtd->bht", q.float(), kf) / (D ** 0.5)
+    s = s.masked_fill(dead, float("-inf"))
+    p = torch.softmax(s, dim=-1).masked_fill(n == 0, 0.0)
+    return torch.einsum("bht,bhtd->bhd", p, vf).to(q.dtype)
+
+
+@torch.no_grad()
+def qkv_rope_append_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                     pos: torch.Tensor, kcache: torch.Tensor,
+                     vcache: torch.Tensor, Hq: int, Hkv: int,
+                     D: int) -> torch.Tensor:
+    """qkv: [B, (Hq+2Hkv)*D], one new token per sequence; pos: [B] int32 on
+    qkv's device; cos/sin: [>= Tmax, D/2]. Rotates q and k of sequence b at
+    pos[b] and writes the roped k and the v copy into cache[b, pos[b]] in
+    place. A row with pos[b] outside [0, Tmax) writes nothing and gets a
+    zero q row (a finished sequence). Returns q [B, Hq, D]."""
+    if qkv.is_cuda:
+        return _require_ext("qkv_rope_append").qkv_rope_append_(
+            qkv.contiguous(), cos, sin, pos, kcache, vcache, Hq, Hkv, D)
+    B = qkv.shape[0]
+    Tmax = kcache.shape[1]
+    if cos.shape[0] < Tmax or sin.shape[0] < Tmax:
+        raise ValueError(
+            f"rope table has {cos.shape[0]} rows, cache needs {Tmax}")
+    live = (pos >= 0) & (pos < Tmax)
+    p = pos.long().clamp(0, Tmax - 1)
+    parts = qkv.view(B, Hq + 2 * Hkv, D).float()
+    cs = cos[p].view(B, 1, D // 2)
+    sn = sin[p].view(B, 1, D // 2)
+
+    def rot(x):
+        x1, x2 = x[..., : D // 2], x[..., D // 2:]
+        return torch.cat([x1 * cs - x2 * sn, x2 * cs + x1 * sn], dim=-1)
+
+    q = rot(parts[:, :Hq]).to(qkv.dtype)
+    q = q.masked_fill(~live.view(B, 1, 1), 0)
+    k = rot(parts[:, Hq:Hq + Hkv]).to(kcache.dtype)
+    v = parts[:, Hq + Hkv:].to(vcache.dtype)
+    rows = torch.nonzero(live).flatten()
+    kcache[rows, p[rows]] = k[rows]
+    vcache[rows, p[rows]] = v[rows]
+    return q
+
+
+# --------------------------------------------------------------------------
 # LayerNorm (GPT-family normalization)
 # --------------------------------------------------------------------------
 class _LayerNormFn(torch.autograd.Function):
@@ -510,4 +608,6 @@ __all__ = [
     "qkv_rope", "qkv_rope_ref", "swiglu", "swiglu_ref",
     "hip_ext_available",
     "grad_sumsq_blocks", "grad_sumsq_", "grad_norm_finalize_",
+    "attention_decode_ragged", "qkv_rope_append_",
+    "decode_ragged_splits", "decode_ragged_chunk",
 ]

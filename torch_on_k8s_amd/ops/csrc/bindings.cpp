@@ -74,6 +74,16 @@ hipError_t tok_attn_decode(const void* q, const void* k, const void* v,
                            void* out, int B, int T, const int* T_dev,
                            int Tmax, int Hq, int Hkv, int D,
                            hipStream_t stream);
+hipError_t tok_attn_decode_ragged(const void* q, const void* k, const void* v,
+                                  const int* lens, void* out, float* ws,
+                                  int B, int Tmax, int Hq, int Hkv, int D,
+                                  int num_splits, int chunk,
+                                  hipStream_t stream);
+hipError_t tok_qkv_rope_append(const void* qkv, void* q, void* kcache,
+                               void* vcache, const float* cos_tab,
+                               const float* sin_tab, const int* pos, int B,
+                               int Tmax, int Hq, int Hkv, int D,
+                               hipStream_t stream);
 hipError_t tok_layernorm_fwd(const void* x, const void* w, const void* b,
                              void* y, float* mu, float* rstd, long nrows,
                              int H, float eps, hipStream_t stream);
@@ -452,6 +462,85 @@ at::Tensor attn_decode(at::Tensor q, at::Tensor kcache, at::Tensor vcache,
   return out;
 }
 
+// q: [B, Hq, D]; kcache/vcache: [B, Tmax, Hkv, D]; lens: [B] int32 on the
+// device, never read by the host. num_splits and chunk come from
+// ops.decode_ragged_splits / ops.decode_ragged_chunk (shapes alone).
+at::Tensor attn_decode_ragged(at::Tensor q, at::Tensor kcache,
+                              at::Tensor vcache, at::Tensor lens,
+                              long num_splits, long chunk) {
+  CHECK_BF16_CUDA(q);
+  CHECK_BF16_CUDA(kcache);
+  CHECK_BF16_CUDA(vcache);
+  TORCH_CHECK(q.dim() == 3 && kcache.dim() == 4, "q [B,Hq,D], cache [B,T,Hkv,D]");
+  const long B = q.size(0), Hq = q.size(1), D = q.size(2);
+  const long Tmax = kcache.size(1), Hkv = kcache.size(2);
+  TORCH_CHECK(kcache.sizes() == vcache.sizes() && kcache.size(0) == B &&
+                  kcache.size(3) == D, "cache shape mismatch");
+  TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
+  TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  const long R = Hq / Hkv;
+  TORCH_CHECK(R == 1 || R == 2 || R == 4 || R == 8,
+              "attn_decode_ragged: Hq/Hkv must be 1, 2, 4 or 8, got ", R);
+  TORCH_CHECK(lens.is_cuda() && lens.scalar_type() == at::kInt &&
+                  lens.is_contiguous() && lens.numel() == B,
+              "lens must be a contiguous int32 GPU tensor of B elements");
+  TORCH_CHECK(Tmax >= 1 && Tmax < (1L << 26), "Tmax out of range");
+  TORCH_CHECK(B >= 1 && B <= 65535 && num_splits >= 1 && num_splits <= 1024,
+              "grid out of range");
+  TORCH_CHECK(chunk >= 1 && num_splits * chunk >= Tmax,
+              "num_splits * chunk must cover Tmax");
+  auto out = at::empty_like(q);
+  at::Tensor ws;
+  float* wsp = nullptr;
+  if (num_splits > 1) {
+    ws = at::empty({B * Hq * num_splits * (D + 2)},
+                   q.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  TOK_HIP_OK(tok_attn_decode_ragged(
+      q.data_ptr(), kcache.data_ptr(), vcache.data_ptr(),
+      lens.data_ptr<int>(), out.data_ptr(), wsp, (int)B, (int)Tmax, (int)Hq,
+      (int)Hkv, (int)D, (int)num_splits, (int)chunk, current_stream()));
+  return out;
+}
+
+// qkv: [B, (Hq+2Hkv)*D], one new token per sequence; pos: [B] int32 on the
+// device. Writes k/v into cache[b, pos[b]] in place and returns roped q.
+at::Tensor qkv_rope_append_(at::Tensor qkv, at::Tensor cos_tab,
+                            at::Tensor sin_tab, at::Tensor pos,
+                            at::Tensor kcache, at::Tensor vcache, long Hq,
+                            long Hkv, long D) {
+  CHECK_BF16_CUDA(qkv);
+  CHECK_BF16_CUDA(kcache);
+  CHECK_BF16_CUDA(vcache);
+  TORCH_CHECK(cos_tab.is_cuda() && cos_tab.scalar_type() == at::kFloat &&
+              cos_tab.is_contiguous());
+  TORCH_CHECK(sin_tab.is_cuda() && sin_tab.scalar_type() == at::kFloat &&
+              sin_tab.is_contiguous());
+  TORCH_CHECK(D % 16 == 0, "head dim must be a multiple of 16");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == (Hq + 2 * Hkv) * D,
+              "packed qkv must be [B, (Hq+2Hkv)*D]");
+  const long B = qkv.size(0);
+  TORCH_CHECK(kcache.dim() == 4 && kcache.sizes() == vcache.sizes() &&
+                  kcache.size(0) == B && kcache.size(2) == Hkv &&
+                  kcache.size(3) == D, "cache shape mismatch");
+  const long Tmax = kcache.size(1);
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt &&
+                  pos.is_contiguous() && pos.numel() == B,
+              "pos must be a contiguous int32 GPU tensor of B elements");
+  TORCH_CHECK(sin_tab.numel() == cos_tab.numel(), "cos/sin shape mismatch");
+  const long table_rows = cos_tab.numel() / (D / 2);
+  TORCH_CHECK(table_rows >= Tmax, "rope table has ", table_rows,
+              " rows, cache needs ", Tmax);
+  auto q = at::empty({B, Hq, D}, qkv.options());
+  TOK_HIP_OK(tok_qkv_rope_append(
+      qkv.data_ptr(), q.data_ptr(), kcache.data_ptr(), vcache.data_ptr(),
+      cos_tab.data_ptr<float>(), sin_tab.data_ptr<float>(),
+      pos.data_ptr<int>(), (int)B, (int)Tmax, (int)Hq, (int)Hkv, (int)D,
+      current_stream()));
+  return q;
+}
+
 std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w,
                                       at::Tensor b, double eps) {
   CHECK_BF16_CUDA(x);
@@ -551,6 +640,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "Single-token KV-cache attention decode (bf16, gfx950)",
           py::arg("q"), py::arg("kcache"), py::arg("vcache"), py::arg("T"),
           py::arg("T_dev") = py::none());
+  mod.def("attn_decode_ragged", &attn_decode_ragged,
+          "Per-sequence-length KV-cache attention decode (bf16, gfx950)",
+          py::arg("q"), py::arg("kcache"), py::arg("vcache"), py::arg("lens"),
+          py::arg("num_splits"), py::arg("chunk"));
+  mod.def("qkv_rope_append_", &qkv_rope_append_,
+          "One-token packed-QKV RoPE + KV-cache append (bf16, gfx950)");
   mod.def("layernorm_bwd", &layernorm_bwd, "LayerNorm backward (bf16, gfx950)");
   mod.def("ce_bwd", &ce_bwd, "Fused cross-entropy backward (bf16, gfx950)");
   mod.def("rmsnorm_fwd", &rmsnorm_fwd, "RMSNorm forward (bf16, gfx950)");

@@ -22,6 +22,9 @@ Endpoints:
                                    "max_new_tokens": 32,
                                    "temperature": 0.0}
                                   returns {"output_ids": [[...]], ...}
+                                  with "ragged": true the prompts may differ
+                                  in length (greedy); "eos_token_id" ends a
+                                  sequence at its first eos
 
 Prompts are token IDs: this framework is tokenizer-free by design
 (synthetic-data training; no network for vocab downloads).
@@ -105,8 +108,12 @@ class InferenceServer:
                            "step": 0})
 
     def generate(self, prompt_ids, max_new_tokens: int = 32,
-                 temperature: float = 0.0):
+                 temperature: float = 0.0, ragged: bool = False,
+                 eos_token_id=None):
         import torch
+        if ragged:
+            return self._generate_ragged(prompt_ids, max_new_tokens,
+                                         eos_token_id)
         dev = next(self.model.parameters()).device
         inp = torch.tensor(prompt_ids, dtype=torch.long, device=dev)
         t0 = time.perf_counter()
@@ -125,6 +132,29 @@ class InferenceServer:
             "tokens_per_s": new.numel() / dt if dt > 0 else None,
         }
 
+    def _generate_ragged(self, prompt_ids, max_new_tokens, eos_token_id):
+        """Prompts of different lengths in one batch (greedy). new_tokens
+        is the true count: a sequence that emitted eos stops there."""
+        import torch
+        t0 = time.perf_counter()
+        with self.lock, torch.no_grad():
+            outs = self.model.generate_ragged(
+                prompt_ids, max_new_tokens=max_new_tokens,
+                eos_token_id=eos_token_id)
+        dt = time.perf_counter() - t0
+        output_ids = [o.tolist() for o in outs]
+        new_ids = [o[len(p):] for o, p in zip(output_ids, prompt_ids)]
+        n_new = sum(len(n) for n in new_ids)
+        self.requests += 1
+        self.tokens_out += n_new
+        return {
+            "output_ids": output_ids,
+            "new_ids": new_ids,
+            "new_tokens": n_new,
+            "latency_s": dt,
+            "tokens_per_s": n_new / dt if dt > 0 else None,
+        }
+
 
 def build_app(srv: InferenceServer):
     from fastapi import FastAPI, HTTPException
@@ -134,6 +164,8 @@ def build_app(srv: InferenceServer):
         prompt_ids: list[list[int]]
         max_new_tokens: int = Field(default=32, ge=1, le=4096)
         temperature: float = Field(default=0.0, ge=0.0, le=10.0)
+        ragged: bool = False
+        eos_token_id: int | None = None
 
     app = FastAPI(title="torch-on-k8s-amd serving")
 
@@ -161,11 +193,38 @@ def build_app(srv: InferenceServer):
         ]
         return PlainTextResponse("\n".join(lines) + "\n")
 
+    def generate_ragged(req, vocab):
+        """ragged=true: lengths may differ; greedy only."""
+        if vocab and any(t < 0 or t >= vocab
+                         for p in req.prompt_ids for t in p):
+            raise HTTPException(400, f"token id out of range [0,{vocab})")
+        if req.eos_token_id is not None and (
+                req.eos_token_id < 0 or
+                (vocab and req.eos_token_id >= vocab)):
+            raise HTTPException(400, f"eos_token_id out of range [0,{vocab})")
+        if req.temperature > 0:
+            raise HTTPException(400, "ragged generation is greedy: "
+                                     "temperature must be 0")
+        max_seq = srv.meta.get("model_config", {}).get("max_seq_len")
+        if max_seq and any(len(p) + req.max_new_tokens > max_seq
+                           for p in req.prompt_ids):
+            raise HTTPException(
+                400, f"prompt+max_new_tokens exceeds the model's trained "
+                     f"context ({max_seq}); RoPE extrapolation beyond it "
+                     f"degrades silently")
+        try:
+            return srv.generate(req.prompt_ids, req.max_new_tokens,
+                                ragged=True, eos_token_id=req.eos_token_id)
+        except NotImplementedError as e:
+            raise HTTPException(400, str(e))
+
     @app.post("/v1/generate")
     def generate(req: GenerateRequest):
         vocab = srv.meta.get("model_config", {}).get("vocab_size")
         if not req.prompt_ids or not all(req.prompt_ids):
             raise HTTPException(400, "prompt_ids must be non-empty")
+        if req.ragged:
+            return generate_ragged(req, vocab)
         if len({len(p) for p in req.prompt_ids}) != 1:
             raise HTTPException(400, "all prompts must share one length")
         if vocab and any(t < 0 or t >= vocab
