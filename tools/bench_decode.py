@@ -13,9 +13,17 @@ in the 256 MB last-level cache, as a decode step over many layers cannot.
 TB/s is the bytes of the VALID K and V rows, each counted once, over time;
 the copy ceiling measured in this repository is 6.29 TB/s.
 
+Sampler level: ``sample_tokens`` against the torch composition it replaces
+(scaled softmax, and with a filter sort, cumsum, mask; then multinomial) and
+against ``argmax``, on bf16 logits [B, V], same captured-loop timing. The
+calls rotate over 4 logits buffers, which stay in the last-level cache as
+the rows the ``lm_head`` GEMM has just written do.
+
 Model level (llama-1b, B=8, 128-token prompts, 128 new tokens, graph on):
-``generate`` against ``generate_ragged`` at equal lengths, and
-``generate_ragged`` at prompt lengths 16..128.
+``generate`` against ``generate_ragged`` at equal lengths,
+``generate_ragged`` at prompt lengths 16..128, and sampling: captured
+``generate_ragged`` sampled (T=0.8, top-k 50, top-p 0.95) against the eager
+``generate(temperature=0.8)``.
 """
 import argparse
 import os
@@ -130,6 +138,72 @@ def kernel_level(args, ops, dev):
             torch.cuda.empty_cache()
 
 
+SAMPLER_VOCABS = (32000, 128256)
+SAMPLER_MIXES = (("temperature", 0, 1.0), ("top-k 50", 50, 1.0),
+                 ("top-p 0.9", 0, 0.9), ("top-k 50 + top-p 0.9", 50, 0.9))
+SAMPLER_T = 0.8
+
+
+def torch_sample(logits, T, k, p):
+    """What one would write without the kernel. Plain temperature is what
+    LlamaModel.generate does; a filter sorts once and cuts both ways."""
+    probs = torch.softmax(logits.float() / T, dim=-1)
+    if not k and p >= 1.0:
+        return torch.multinomial(probs, 1)
+    sp, si = torch.sort(probs, dim=-1, descending=True)
+    if k:
+        sp[:, k:] = 0.0
+    if p < 1.0:
+        cum = torch.cumsum(sp, dim=-1)
+        sp = sp.masked_fill(cum - sp >= p * cum[:, -1:], 0.0)
+    return si.gather(1, torch.multinomial(sp, 1))
+
+
+def sampler_level(args, ops, dev):
+    print(f"\n# sampler level: bf16 logits [B, V], T={SAMPLER_T}, us per "
+          f"call as median [min..max] over {args.rounds} rounds; x = torch "
+          f"composition / sample_tokens")
+    nbuf, iters = 4, 100
+    for V in SAMPLER_VOCABS:
+        for B in args.B:
+            g = torch.Generator(device=dev).manual_seed(0)
+            logits = (4 * torch.randn(nbuf, B, V, device=dev, generator=g)
+                      ).bfloat16()
+            temp = torch.full((B,), SAMPLER_T, device=dev)
+            seed = torch.arange(B, device=dev)
+            ctr = torch.arange(B, device=dev, dtype=torch.int32)
+            cfgs, fns = [("argmax", None)], [lambda i: logits[i].argmax(-1)]
+            for name, k, p in SAMPLER_MIXES:
+                kt = torch.full((B,), k, dtype=torch.int32, device=dev)
+                pt = torch.full((B,), p, device=dev)
+                cfgs.append((f"sample_tokens {name}", name))
+                fns.append(lambda i, kt=kt, pt=pt: ops.sample_tokens(
+                    logits[i], temp, kt, pt, seed, ctr))
+                cfgs.append((f"torch {name}", name))
+                fns.append(lambda i, k=k, p=p: torch_sample(
+                    logits[i], SAMPLER_T, k, p))
+            for fn in fns:
+                for i in range(nbuf):
+                    fn(i)
+            torch.cuda.synchronize()
+            graphs = [capture_calls(fn, nbuf, iters) for fn in fns]
+            for gr in graphs:
+                gr.replay()
+            torch.cuda.synchronize()
+            times = [[] for _ in cfgs]
+            for _ in range(args.rounds):
+                for j, gr in enumerate(graphs):
+                    times[j].append(time_graph(gr, iters))
+            del graphs
+            print(f"\nB={B} V={V} buffers={nbuf} iters={iters}")
+            med = {n: statistics.median(t) for (n, _), t in zip(cfgs, times)}
+            for (name, mix), ts in zip(cfgs, times):
+                tail = ""
+                if name.startswith("torch"):
+                    tail = f"  {med[name] / med['sample_tokens ' + mix]:5.1f}x"
+                print(f"  {name:36s} {fmt(ts)} us{tail}", flush=True)
+
+
 def model_level(args, dev):
     from torch_on_k8s_amd.models.llama import LlamaModel, get_config
     torch.manual_seed(0)
@@ -150,6 +224,14 @@ def model_level(args, dev):
         (f"generate_ragged (lens {min(lens)}..{max(lens)})",
          lambda: model.generate_ragged(ragged, max_new_tokens=N,
                                        use_graph=True)),
+        ("generate_ragged sampled (equal)", lambda: model.generate_ragged(
+            equal, max_new_tokens=N, use_graph=True, temperature=0.8,
+            top_k=50, top_p=0.95, seed=1)),
+        ("generate_ragged T=0.8 only (equal)", lambda: model.generate_ragged(
+            equal, max_new_tokens=N, use_graph=True, temperature=0.8,
+            seed=1)),
+        ("generate temperature=0.8 (eager)", lambda: model.generate(
+            ids, max_new_tokens=N, temperature=0.8)),
     ]
     for _, fn in runs:        # warm: code objects, GEMM algorithm choice
         fn()
@@ -185,6 +267,7 @@ def main():
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--new-tokens", type=int, default=128)
     ap.add_argument("--skip-kernel", action="store_true")
+    ap.add_argument("--skip-sampler", action="store_true")
     ap.add_argument("--skip-model", action="store_true")
     args = ap.parse_args()
     if args.rounds < 3:
@@ -195,6 +278,8 @@ def main():
     dev = torch.device("cuda", 0)
     if not args.skip_kernel:
         kernel_level(args, ops, dev)
+    if not args.skip_sampler:
+        sampler_level(args, ops, dev)
     if not args.skip_model:
         model_level(args, dev)
 

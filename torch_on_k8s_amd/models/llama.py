@@ -15,6 +15,7 @@ metric). Design choices for MI355X:
 """
 from __future__ import annotations
 
+import secrets
 from dataclasses import dataclass, asdict
 
 import torch
@@ -345,11 +346,22 @@ class LlamaModel(nn.Module):
     def generate_ragged(self, prompts, max_new_tokens: int = 32,
                         eos_token_id: int | None = None,
                         use_graph: bool | None = None,
-                        pad_token_id: int = 0) -> list[torch.Tensor]:
-        """Greedy generation for prompts of different lengths (each a 1-D
-        id tensor or a list of ids, length >= 1). Returns one 1-D tensor
-        per sequence: the prompt followed by its new tokens, ending at the
+                        pad_token_id: int = 0, *,
+                        temperature=0.0, top_k=0, top_p=1.0,
+                        seed=None) -> list[torch.Tensor]:
+        """Generation for prompts of different lengths (each a 1-D id
+        tensor or a list of ids, length >= 1). Returns one 1-D tensor per
+        sequence: the prompt followed by its new tokens, ending at the
         first eos_token_id (inclusive) if one is given and emitted.
+
+        temperature / top_k / top_p / seed are scalars or one value per
+        prompt. With every temperature 0 (the default) the tokens are the
+        argmax. Otherwise every token is drawn by ops.sample_tokens, also
+        inside the captured step; a row with temperature 0 stays greedy.
+        An int seed s gives row b the seed s + b; seed=None draws one from
+        `secrets`. The draw for the token at index i of a sequence depends
+        on (that row's seed, i) alone: not on the batch slot, the step
+        number or whether the step ran eagerly or as a graph replay.
 
         Prefill right-pads to the longest prompt and runs the causal
         flash-attention kernel: a valid row never sees a pad key, and the
@@ -361,6 +373,28 @@ class LlamaModel(nn.Module):
         cfg = self.cfg
         dev = self.embed_tokens.weight.device
         dtype = self.embed_tokens.weight.dtype
+        B = len(prompts)
+
+        def per_row(name, value):
+            if isinstance(value, (list, tuple)):
+                if len(value) != B:
+                    raise ValueError(f"{name}: {len(value)} values for {B} "
+                                     f"prompts")
+                return list(value)
+            return [value] * B
+
+        temps = [float(t) for t in per_row("temperature", temperature)]
+        sampled = any(t > 0 for t in temps)
+        if sampled:
+            # host RNG before any GPU work; int64 two's complement
+            if seed is None:
+                seed = secrets.randbits(63)
+            seeds = (list(seed) if isinstance(seed, (list, tuple))
+                     else [int(seed) + b for b in range(B)])
+            if len(seeds) != B:
+                raise ValueError(f"seed: {len(seeds)} values for {B} prompts")
+            seeds = [(int(s) + 2 ** 63) % 2 ** 64 - 2 ** 63 for s in seeds]
+
         seqs = [torch.as_tensor(p, dtype=torch.long).reshape(-1).to(dev)
                 for p in prompts]
         if not seqs or any(s.numel() < 1 for s in seqs):
@@ -368,7 +402,22 @@ class LlamaModel(nn.Module):
                              "length >= 1")
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
-        B = len(seqs)
+        if sampled:
+            temp_t = torch.tensor(temps, dtype=torch.float32, device=dev)
+            topk_t = torch.tensor([int(k) for k in per_row("top_k", top_k)],
+                                  dtype=torch.int32, device=dev)
+            topp_t = torch.tensor([float(p) for p in per_row("top_p", top_p)],
+                                  dtype=torch.float32, device=dev)
+            seed_t = torch.tensor(seeds, dtype=torch.long, device=dev)
+
+        def pick(logits, index):
+            """Next token per row of logits [B, V]; index [B] is where in
+            its sequence each token will sit (the draw's counter)."""
+            if not sampled:
+                return logits.argmax(-1)
+            return ops.sample_tokens(logits, temp_t, topk_t, topp_t, seed_t,
+                                     index)
+
         lens0 = torch.tensor([s.numel() for s in seqs], device=dev)
         S0 = int(max(s.numel() for s in seqs))
         Tmax = S0 + max_new_tokens
@@ -394,7 +443,7 @@ class LlamaModel(nn.Module):
             x = x + blk.attn.o_proj(o.reshape(B, S0, Hq * D))
             x = x + blk.mlp(blk.post_attn_norm(x))
         last = x[torch.arange(B, device=dev), lens0 - 1].unsqueeze(1)
-        first = self.lm_head(self.norm(last))[:, -1].argmax(-1, keepdim=True)
+        first = pick(self.lm_head(self.norm(last))[:, -1], lens0).unsqueeze(1)
 
         # Decode state, all on the device. token_buf holds the token to
         # feed; it sits at position pos = lens - 1 and attends to lens rows.
@@ -417,7 +466,7 @@ class LlamaModel(nn.Module):
                 o = ops.attention_decode_ragged(q, kc[i], vc[i], lens)
                 x = x + blk.attn.o_proj(o.view(B, 1, Hq * D))
                 x = x + blk.mlp(blk.post_attn_norm(x))
-            nxt = self.lm_head(self.norm(x))[:, -1].argmax(-1)
+            nxt = pick(self.lm_head(self.norm(x))[:, -1], lens)
             nxt = torch.where(finished, eos, nxt)
             finished.logical_or_(nxt == eos)
             token_buf.copy_(nxt.unsqueeze(1))  # self-feed the next replay

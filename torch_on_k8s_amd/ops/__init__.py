@@ -528,6 +528,103 @@ def qkv_rope_append_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
 
 
 # --------------------------------------------------------------------------
+# Token sampling: temperature / top-k / top-p, one draw per row (no autograd)
+# --------------------------------------------------------------------------
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on Python ints: counter 4 words, key 2 words -> 4 words."""
+    c0, c1, c2, c3 = (int(c) & _M32 for c in counter)
+    k0, k1 = (int(k) & _M32 for k in key)
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0, p1 & _M32,
+                          (p0 >> 32) ^ c3 ^ k1, p0 & _M32)
+        k0, k1 = (k0 + _PHILOX_W0) & _M32, (k1 + _PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def sample_uniform(seed: int, counter: int) -> float:
+    """The draw of sample_tokens for one row: key = (low, high) words of
+    seed, counter = (low, high words of counter, 0, 0), u = (word 0 >> 8) *
+    2^-24, in [0, 1)."""
+    s, c = int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1)
+    w = philox4x32_10((c & _M32, c >> 32, 0, 0), (s & _M32, s >> 32))
+    return (w[0] >> 8) * 2.0 ** -24
+
+
+def _sample_row_cpu(l: torch.Tensor, T: float, k: int, p: float,
+                    u: float) -> int:
+    V = l.numel()
+    if not T > 0:
+        return int(torch.argmax(l))        # first index of the maximum
+    top = l.max()
+    if not torch.isfinite(top):            # NaN, +inf or nothing finite:
+        return int(torch.argmax(l))        # unspecified, but in range
+    e = torch.exp((l - top) / T)           # exp(-inf) = 0
+    keep = torch.ones(V, dtype=torch.bool)
+    if 0 < k < V:
+        keep &= l >= torch.topk(l, k).values[-1]
+    if p < 1:
+        vals, inv = torch.unique(l[keep], return_inverse=True)  # ascending
+        mass = torch.zeros(vals.numel(), dtype=l.dtype).index_add_(
+            0, inv, e[keep])
+        cum = torch.cumsum(mass.flip(0), 0)                     # descending
+        hit = torch.nonzero(cum >= p * cum[-1]).flatten()
+        at = int(hit[0]) if hit.numel() and p > 0 else 0
+        keep &= l >= vals.flip(0)[at]
+    C = torch.cumsum(torch.where(keep, e, torch.zeros_like(e)), 0)
+    hit = torch.nonzero(keep & (C > u * C[-1])).flatten()
+    if hit.numel():
+        return int(hit[0])
+    return int(torch.nonzero(keep & (e > 0)).flatten()[-1])
+
+
+@torch.no_grad()
+def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor,
+                  top_k: torch.Tensor, top_p: torch.Tensor,
+                  seed: torch.Tensor, counter: torch.Tensor, *,
+                  u: torch.Tensor | None = None) -> torch.Tensor:
+    """One token per row of logits [B, V] (unit stride in V, any row
+    stride; bf16 on the GPU). temperature / top_p: [B] fp32, top_k: [B]
+    int32, seed: [B] int64, counter: [B] int32 or int64, all on the logits'
+    device and never read by the host, so the call can be captured and a
+    replay follows new contents. Returns int64 [B].
+
+    Row b: temperature <= 0 gives the lowest index of the maximum logit and
+    ignores the rest. Otherwise e_i = exp((l_i - max l) / T); 0 < top_k < V
+    keeps the logits >= the k-th largest (ties kept); top_p < 1 then keeps
+    the logits >= the first distinct value, descending, at which the
+    cumulative mass reaches top_p * (surviving mass), top_p <= 0 the top
+    tie group only. With C the running sum of the kept e_i in index order
+    and M its total, the result is the first kept index with C_i > u * M
+    (the last kept index of nonzero mass if rounding leaves none), where u =
+    sample_uniform(seed[b], counter[b]) unless `u` ([B] fp32 in [0, 1)) is
+    given. The same row gives the same token in any slot of any batch."""
+    if logits.dim() != 2:
+        raise ValueError("sample_tokens: logits must be [B, V]")
+    if logits.is_cuda:
+        if logits.dtype != torch.bfloat16:
+            raise TypeError(
+                f"sample_tokens: GPU logits must be bfloat16, got "
+                f"{logits.dtype}")
+        return _require_ext("sample_tokens").sample_tokens(
+            logits, temperature, top_k, top_p, seed, counter, u)
+    B = logits.shape[0]
+    out = torch.empty(B, dtype=torch.long)
+    lf = logits.double()
+    for b in range(B):
+        ub = (float(u[b]) if u is not None
+              else sample_uniform(int(seed[b]), int(counter[b])))
+        out[b] = _sample_row_cpu(lf[b], float(temperature[b]), int(top_k[b]),
+                                 float(top_p[b]), ub)
+    return out
+
+
+# --------------------------------------------------------------------------
 # LayerNorm (GPT-family normalization)
 # --------------------------------------------------------------------------
 class _LayerNormFn(torch.autograd.Function):
@@ -610,4 +707,5 @@ __all__ = [
     "grad_sumsq_blocks", "grad_sumsq_", "grad_norm_finalize_",
     "attention_decode_ragged", "qkv_rope_append_",
     "decode_ragged_splits", "decode_ragged_chunk",
+    "sample_tokens", "sample_uniform", "philox4x32_10",
 ]

@@ -84,6 +84,13 @@ hipError_t tok_qkv_rope_append(const void* qkv, void* q, void* kcache,
                                const float* sin_tab, const int* pos, int B,
                                int Tmax, int Hq, int Hkv, int D,
                                hipStream_t stream);
+int tok_sample_max_vocab();
+hipError_t tok_sample_tokens(const void* logits, long row_stride,
+                             const float* temperature, const int* top_k,
+                             const float* top_p, const long long* seed,
+                             const void* counter, int counter_is_64,
+                             const float* u_opt, long long* out, int B, int V,
+                             hipStream_t stream);
 hipError_t tok_layernorm_fwd(const void* x, const void* w, const void* b,
                              void* y, float* mu, float* rstd, long nrows,
                              int H, float eps, hipStream_t stream);
@@ -541,6 +548,51 @@ at::Tensor qkv_rope_append_(at::Tensor qkv, at::Tensor cos_tab,
   return q;
 }
 
+// logits: [B, V] bf16, unit stride in V, any row stride. The per-row
+// parameters are [B] device tensors that the host never reads; u replaces
+// the generator's draw when given. Returns int64 [B].
+at::Tensor sample_tokens(at::Tensor logits, at::Tensor temperature,
+                         at::Tensor top_k, at::Tensor top_p, at::Tensor seed,
+                         at::Tensor counter, c10::optional<at::Tensor> u) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kBFloat16 &&
+                  logits.dim() == 2,
+              "sample_tokens: logits must be a [B, V] bf16 GPU tensor");
+  const long B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(B >= 1 && V >= 1 && V <= tok_sample_max_vocab(),
+              "sample_tokens: need B >= 1 and 1 <= V <= ",
+              tok_sample_max_vocab());
+  TORCH_CHECK(logits.stride(1) == 1 || V == 1,
+              "sample_tokens: logits must have unit stride in V");
+  auto row_ok = [&](const at::Tensor& t, at::ScalarType ty, const char* n) {
+    TORCH_CHECK(t.is_cuda() && t.get_device() == logits.get_device() &&
+                    t.scalar_type() == ty && t.is_contiguous() &&
+                    t.numel() == B,
+                "sample_tokens: ", n, " must be a contiguous [B] tensor of ",
+                c10::toString(ty), " on the logits' device");
+  };
+  row_ok(temperature, at::kFloat, "temperature");
+  row_ok(top_k, at::kInt, "top_k");
+  row_ok(top_p, at::kFloat, "top_p");
+  row_ok(seed, at::kLong, "seed");
+  const bool c64 = counter.scalar_type() == at::kLong;
+  row_ok(counter, c64 ? at::kLong : at::kInt, "counter");
+  const float* up = nullptr;
+  if (u.has_value()) {
+    row_ok(*u, at::kFloat, "u");
+    up = u->data_ptr<float>();
+  }
+  auto out = at::empty({B}, logits.options().dtype(at::kLong));
+  TOK_HIP_OK(tok_sample_tokens(
+      logits.data_ptr(), B > 1 ? logits.stride(0) : 0,
+      temperature.data_ptr<float>(), top_k.data_ptr<int>(),
+      top_p.data_ptr<float>(),
+      reinterpret_cast<const long long*>(seed.data_ptr<int64_t>()),
+      counter.data_ptr(), c64 ? 1 : 0, up,
+      reinterpret_cast<long long*>(out.data_ptr<int64_t>()), (int)B, (int)V,
+      current_stream()));
+  return out;
+}
+
 std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w,
                                       at::Tensor b, double eps) {
   CHECK_BF16_CUDA(x);
@@ -646,6 +698,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("num_splits"), py::arg("chunk"));
   mod.def("qkv_rope_append_", &qkv_rope_append_,
           "One-token packed-QKV RoPE + KV-cache append (bf16, gfx950)");
+  mod.def("sample_tokens", &sample_tokens,
+          "Fused temperature / top-k / top-p sampler (bf16, gfx950)",
+          py::arg("logits"), py::arg("temperature"), py::arg("top_k"),
+          py::arg("top_p"), py::arg("seed"), py::arg("counter"),
+          py::arg("u") = py::none());
   mod.def("layernorm_bwd", &layernorm_bwd, "LayerNorm backward (bf16, gfx950)");
   mod.def("ce_bwd", &ce_bwd, "Fused cross-entropy backward (bf16, gfx950)");
   mod.def("rmsnorm_fwd", &rmsnorm_fwd, "RMSNorm forward (bf16, gfx950)");

@@ -23,8 +23,11 @@ Endpoints:
                                    "temperature": 0.0}
                                   returns {"output_ids": [[...]], ...}
                                   with "ragged": true the prompts may differ
-                                  in length (greedy); "eos_token_id" ends a
-                                  sequence at its first eos
+                                  in length; "eos_token_id" ends a sequence
+                                  at its first eos; "temperature", "top_k",
+                                  "top_p" and "seed" sample inside the
+                                  captured decode step, and the response
+                                  carries the "seed" that was used
 
 Prompts are token IDs: this framework is tokenizer-free by design
 (synthetic-data training; no network for vocab downloads).
@@ -36,6 +39,7 @@ of a function-local class break that resolution.
 import argparse
 import json
 import os
+import secrets
 import threading
 import time
 
@@ -109,11 +113,13 @@ class InferenceServer:
 
     def generate(self, prompt_ids, max_new_tokens: int = 32,
                  temperature: float = 0.0, ragged: bool = False,
-                 eos_token_id=None):
+                 eos_token_id=None, top_k: int = 0, top_p: float = 1.0,
+                 seed=None):
         import torch
         if ragged:
             return self._generate_ragged(prompt_ids, max_new_tokens,
-                                         eos_token_id)
+                                         eos_token_id, temperature, top_k,
+                                         top_p, seed)
         dev = next(self.model.parameters()).device
         inp = torch.tensor(prompt_ids, dtype=torch.long, device=dev)
         t0 = time.perf_counter()
@@ -132,15 +138,22 @@ class InferenceServer:
             "tokens_per_s": new.numel() / dt if dt > 0 else None,
         }
 
-    def _generate_ragged(self, prompt_ids, max_new_tokens, eos_token_id):
-        """Prompts of different lengths in one batch (greedy). new_tokens
-        is the true count: a sequence that emitted eos stops there."""
+    def _generate_ragged(self, prompt_ids, max_new_tokens, eos_token_id,
+                         temperature=0.0, top_k=0, top_p=1.0, seed=None):
+        """Prompts of different lengths in one batch. new_tokens is the
+        true count: a sequence that emitted eos stops there. A sampled
+        request (temperature > 0) without a seed gets one here, and the
+        response carries it: row b draws with seed + b."""
         import torch
+        sampled = temperature > 0
+        if sampled and seed is None:
+            seed = secrets.randbits(63)
         t0 = time.perf_counter()
         with self.lock, torch.no_grad():
             outs = self.model.generate_ragged(
                 prompt_ids, max_new_tokens=max_new_tokens,
-                eos_token_id=eos_token_id)
+                eos_token_id=eos_token_id, temperature=temperature,
+                top_k=top_k, top_p=top_p, seed=seed)
         dt = time.perf_counter() - t0
         output_ids = [o.tolist() for o in outs]
         new_ids = [o[len(p):] for o, p in zip(output_ids, prompt_ids)]
@@ -153,6 +166,7 @@ class InferenceServer:
             "new_tokens": n_new,
             "latency_s": dt,
             "tokens_per_s": n_new / dt if dt > 0 else None,
+            "seed": seed if sampled else None,
         }
 
 
@@ -166,6 +180,9 @@ def build_app(srv: InferenceServer):
         temperature: float = Field(default=0.0, ge=0.0, le=10.0)
         ragged: bool = False
         eos_token_id: int | None = None
+        top_k: int = 0
+        top_p: float = 1.0
+        seed: int | None = None
 
     app = FastAPI(title="torch-on-k8s-amd serving")
 
@@ -194,7 +211,8 @@ def build_app(srv: InferenceServer):
         return PlainTextResponse("\n".join(lines) + "\n")
 
     def generate_ragged(req, vocab):
-        """ragged=true: lengths may differ; greedy only."""
+        """ragged=true: lengths may differ; greedy, or sampled with
+        temperature / top_k / top_p / seed."""
         if vocab and any(t < 0 or t >= vocab
                          for p in req.prompt_ids for t in p):
             raise HTTPException(400, f"token id out of range [0,{vocab})")
@@ -202,9 +220,6 @@ def build_app(srv: InferenceServer):
                 req.eos_token_id < 0 or
                 (vocab and req.eos_token_id >= vocab)):
             raise HTTPException(400, f"eos_token_id out of range [0,{vocab})")
-        if req.temperature > 0:
-            raise HTTPException(400, "ragged generation is greedy: "
-                                     "temperature must be 0")
         max_seq = srv.meta.get("model_config", {}).get("max_seq_len")
         if max_seq and any(len(p) + req.max_new_tokens > max_seq
                            for p in req.prompt_ids):
@@ -214,7 +229,10 @@ def build_app(srv: InferenceServer):
                      f"degrades silently")
         try:
             return srv.generate(req.prompt_ids, req.max_new_tokens,
-                                ragged=True, eos_token_id=req.eos_token_id)
+                                temperature=req.temperature, ragged=True,
+                                eos_token_id=req.eos_token_id,
+                                top_k=req.top_k, top_p=req.top_p,
+                                seed=req.seed)
         except NotImplementedError as e:
             raise HTTPException(400, str(e))
 
@@ -223,8 +241,17 @@ def build_app(srv: InferenceServer):
         vocab = srv.meta.get("model_config", {}).get("vocab_size")
         if not req.prompt_ids or not all(req.prompt_ids):
             raise HTTPException(400, "prompt_ids must be non-empty")
+        if req.top_k < 0:
+            raise HTTPException(400, "top_k must be >= 0")
+        if not 0.0 < req.top_p <= 1.0:
+            raise HTTPException(400, "top_p must be in (0, 1]")
+        if req.seed is not None and not -2 ** 63 <= req.seed < 2 ** 63:
+            raise HTTPException(400, "seed must fit a signed 64-bit integer")
         if req.ragged:
             return generate_ragged(req, vocab)
+        if req.top_k != 0 or req.top_p != 1.0 or req.seed is not None:
+            raise HTTPException(400, 'sampling controls (top_k, top_p, seed) '
+                                     'need "ragged": true')
         if len({len(p) for p in req.prompt_ids}) != 1:
             raise HTTPException(400, "all prompts must share one length")
         if vocab and any(t < 0 or t >= vocab
