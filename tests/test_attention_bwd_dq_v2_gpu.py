@@ -19,6 +19,7 @@ import functools
 import pytest
 import torch
 
+import kernel_oracle_attention as ka
 from torch_on_k8s_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -64,7 +65,8 @@ def problem(B, S, Hq, Hkv, D, causal, spiked=False):
     kr = k.clone().requires_grad_(True)
     vr = v.clone().requires_grad_(True)
     ops.attention_ref(qr, kr, vr, causal).float().backward(do)
-    return (q, k, v, do), (qr.grad, kr.grad, vr.grad)
+    return (q, k, v, do), (qr.grad, kr.grad, vr.grad), \
+        ka.of_floats(q, k, v, do, causal)
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,7 +74,7 @@ def hip_grads(case, spiked, dq_variant):
     """(dq, dk, dv) of one case through one dQ variant; dq_variant None is
     the call without the selector."""
     causal = case[5]
-    (q, k, v, do), _ = problem(*case, spiked=spiked)
+    (q, k, v, do), _, _ = problem(*case, spiked=spiked)
     qg, kg, vg, dog = (t.bfloat16().to(dev()) for t in (q, k, v, do))
     o, lse = ops._C.attn_fwd(qg, kg, vg, causal)
     if dq_variant is None:
@@ -81,7 +83,7 @@ def hip_grads(case, spiked, dq_variant):
 
 
 def check(case, dq_variant, spiked=False):
-    _, refs = problem(*case, spiked=spiked)
+    _, refs, specs = problem(*case, spiked=spiked)
     grads = hip_grads(case, spiked, dq_variant)
     for name, g_hip, g_ref in zip(("dq", "dk", "dv"), grads, refs):
         g = g_hip.float().cpu()
@@ -91,6 +93,8 @@ def check(case, dq_variant, spiked=False):
         print(f"{name} dq_variant={dq_variant} max err {err:.5f} (bound "
               f"{0.04 * scale:.5f})")
         assert err < 0.04 * scale, f"{name} max err {err} (scale {scale})"
+    ka.check_all(f"bwd_dq_file.dq_variant={dq_variant}[{case},spiked={spiked}]",
+                 dict(zip(("dq", "dk", "dv"), grads)), specs)
 
 
 def check_variants_agree(case, spiked=False):
@@ -138,7 +142,7 @@ def test_default_backward_dq():
 
 def test_dq_variant_is_checked():
     case = CASES[0]
-    (q, k, v, do), _ = problem(*case)
+    (q, k, v, do), _, _ = problem(*case)
     qg, kg, vg, dog = (t.bfloat16().to(dev()) for t in (q, k, v, do))
     o, lse = ops._C.attn_fwd(qg, kg, vg, True)
     with pytest.raises(RuntimeError):

@@ -12,6 +12,7 @@ import functools
 import pytest
 import torch
 
+import kernel_oracle_attention as ka
 from torch_on_k8s_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -53,12 +54,13 @@ def problem(B, S, Hq, Hkv, D, causal, spiked=False):
     kr = k.clone().requires_grad_(True)
     vr = v.clone().requires_grad_(True)
     ops.attention_ref(qr, kr, vr, causal).float().backward(do)
-    return (q, k, v, do), (qr.grad, kr.grad, vr.grad)
+    return (q, k, v, do), (qr.grad, kr.grad, vr.grad), \
+        ka.of_floats(q, k, v, do, causal)
 
 
 def check(case, split, spiked=False):
     causal = case[5]
-    (q, k, v, do), refs = problem(*case, spiked=spiked)
+    (q, k, v, do), refs, specs = problem(*case, spiked=spiked)
     qg, kg, vg, dog = (t.bfloat16().to(dev()) for t in (q, k, v, do))
     o, lse = ops._C.attn_fwd(qg, kg, vg, causal)
     grads = ops._C.attn_bwd(qg, kg, vg, o, lse, dog, causal, split)
@@ -70,6 +72,8 @@ def check(case, split, spiked=False):
         print(f"{name} split={split} max err {err:.5f} (bound "
               f"{0.04 * scale:.5f})")
         assert err < 0.04 * scale, f"{name} max err {err} (scale {scale})"
+    ka.check_all(f"bwd_fused_file.split={split}[{case},spiked={spiked}]",
+                 dict(zip(("dq", "dk", "dv"), grads)), specs)
 
 
 @pytest.mark.parametrize("split", [False, True], ids=["fused", "split"])
@@ -88,7 +92,7 @@ def test_default_backward_is_fused():
     bitwise those of an explicit split=False call."""
     case = CASES[3]
     causal = case[5]
-    (q, k, v, do), _ = problem(*case)
+    (q, k, v, do), _, _ = problem(*case)
     qg, kg, vg, dog = (t.bfloat16().to(dev()) for t in (q, k, v, do))
     o, lse = ops._C.attn_fwd(qg, kg, vg, causal)
     _, dk_f, dv_f = ops._C.attn_bwd(qg, kg, vg, o, lse, dog, causal, False)

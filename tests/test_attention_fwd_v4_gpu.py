@@ -2,15 +2,16 @@
 and the v3 kernel it replaces (variant 1), each against the reference.
 
 O: ops.attention_ref in fp32 on bf16-quantised inputs, bounds as in
-test_attention_gpu.py (0.03 max-abs, 0.05 for the spiked inputs).
+test_attention_gpu.py (0.03 max-abs, 0.05 for the spiked inputs), and per
+element the fp64 reference and rule of kernel_oracle_attention.py.
 
 LSE: an fp64 logsumexp of the scaled, masked scores of the same inputs.
  * v3 (variant 1) must stay inside a worst-case fp32 bound: a score is a
    D-term fp32 sum and l an S-term one, so |err| <= (D + S) * 2^-24 *
    max(1, |score|max), with a floor of 1e-5 for the hardware log/exp.
- * v4 (variant 0) is allowed 4x the error v3 shows on the same inputs,
-   floor 1e-5: both accumulate in fp32, in a different order. A slip
-   between the log2 and the natural-log domain shows up at 1e-2 or worse.
+ * v4 (variant 0) is judged per element by the rule of
+   kernel_oracle_attention.py, as v3 is too; v4 is no longer measured
+   against v3, which is itself a kernel under test.
 
 The shapes are the smallest that reach each path of the kernel; see CASES.
 """
@@ -19,6 +20,7 @@ import functools
 import pytest
 import torch
 
+import kernel_oracle_attention as ka
 from torch_on_k8s_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -80,11 +82,12 @@ def problem(B, S, Hq, Hkv, D, causal, kind="random"):
         c = torch.tensor([0.0, 2.5, 5.5, 5.5]).repeat_interleave(64)
         q = torch.full((B, S, Hq, D), 0.25)
         k = c.view(1, S, 1, 1).expand(B, S, Hkv, D).contiguous()
-    return (q, k, v), references(q, k, v, causal)
+    return (q, k, v), references(q, k, v, causal), \
+        ka.of_floats(q, k, v, None, causal)
 
 
 def run_fwd(case, kind, variant):
-    (q, k, v), _ = problem(*case, kind=kind)
+    (q, k, v), _, _ = problem(*case, kind=kind)
     qg, kg, vg = (t.bfloat16().to(dev()) for t in (q, k, v))
     o, lse = ops._C.attn_fwd(qg, kg, vg, case[5], variant)
     return o.float().cpu(), lse.double().cpu()
@@ -92,26 +95,20 @@ def run_fwd(case, kind, variant):
 
 def check(case, kind, variant, o_bound):
     B, S, Hq, Hkv, D, causal = case
-    _, (o_ref, lse_ref, smax) = problem(*case, kind=kind)
+    _, (o_ref, lse_ref, smax), specs = problem(*case, kind=kind)
     o, lse = run_fwd(case, kind, variant)
     assert torch.isfinite(o).all(), "O has non-finite values"
     assert torch.isfinite(lse).all(), "LSE has non-finite values"
     o_err = (o - o_ref).abs().max().item()
     lse_err = (lse - lse_ref).abs().max().item()
     fp32_bound = max(1e-5, (D + S) * 2.0 ** -24 * max(1.0, smax))
-    if variant == 1:
-        lse_bound = fp32_bound
-        print(f"variant 1: O err {o_err:.5f} (bound {o_bound}); LSE err "
-              f"{lse_err:.3e} (bound {lse_bound:.3e})")
-    else:
-        _, lse3 = run_fwd(case, kind, 1)
-        err3 = (lse3 - lse_ref).abs().max().item()
-        lse_bound = max(4.0 * err3, 1e-5)
-        print(f"variant 0: O err {o_err:.5f} (bound {o_bound}); LSE err "
-              f"{lse_err:.3e}, v3 LSE err {err3:.3e} (bound "
-              f"{lse_bound:.3e})")
+    print(f"variant {variant}: O err {o_err:.5f} (bound {o_bound}); LSE err "
+          f"{lse_err:.3e} (v3 bound {fp32_bound:.3e})")
     assert o_err < o_bound, f"O max err {o_err}"
-    assert lse_err <= lse_bound, f"LSE max err {lse_err} > {lse_bound}"
+    if variant == 1:
+        assert lse_err <= fp32_bound, f"LSE max err {lse_err} > {fp32_bound}"
+    ka.check_all(f"fwd_v4_file.variant{variant}[{case},{kind}]",
+                 {"o": o, "lse": lse}, specs)
 
 
 @pytest.mark.parametrize("variant", [0, 1], ids=["v4", "v3"])
@@ -132,7 +129,7 @@ def test_attn_fwd_spiked(variant):
 
 def test_default_forward_is_v4():
     """ops.attention (no selector) runs variant 0: bitwise the same O."""
-    (q, k, v), _ = problem(*CASES[1])
+    (q, k, v), _, _ = problem(*CASES[1])
     qg, kg, vg = (t.bfloat16().to(dev()) for t in (q, k, v))
     o0, _ = ops._C.attn_fwd(qg, kg, vg, True, 0)
     assert torch.equal(ops.attention(qg, kg, vg, True), o0)
@@ -162,3 +159,6 @@ def test_attn_backward_through_v4():
         scale = max(1.0, g_ref.abs().max().item())
         print(f"{name} max err {err:.5f} (bound {0.04 * scale:.5f})")
         assert err < 0.04 * scale, f"{name} max err {err} (scale {scale})"
+    ka.check_all("bwd_through_v4",
+                 {"dq": qg.grad, "dk": kg.grad, "dv": vg.grad},
+                 ka.of_floats(q, k, v, do, causal))

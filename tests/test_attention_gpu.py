@@ -1,11 +1,13 @@
 """GPU numerics: gfx950 flash-attention kernel vs fp32 reference.
 
 Reference = ops.attention_ref (plain PyTorch fp32 on CPU) with
-bf16-quantized inputs, per the repo test policy.
+bf16-quantized inputs, per the repo test policy; and, per element, the
+fp64 reference and rule of kernel_oracle_attention.py.
 """
 import pytest
 import torch
 
+import kernel_oracle_attention as ka
 from torch_on_k8s_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -40,6 +42,7 @@ def test_attn_forward(B, S, Hq, Hkv, D, causal):
                        v.bfloat16().to(dev()), causal)
     err = (og.float().cpu() - o_ref).abs().max().item()
     assert err < 0.03, f"forward max err {err}"
+    ka.check("attention.o", og, ka.of_floats(q, k, v, None, causal)["o"])
 
 
 @pytest.mark.parametrize("B,S,Hq,Hkv,D,causal", CASES)
@@ -64,6 +67,8 @@ def test_attn_backward(B, S, Hq, Hkv, D, causal):
         err = (g_hip.float().cpu() - g_ref).abs().max().item()
         scale = max(1.0, g_ref.abs().max().item())
         assert err < 0.04 * scale, f"{name} max err {err} (scale {scale})"
+    ka.check_all("attention", {"dq": qg.grad, "dk": kg.grad, "dv": vg.grad},
+                 ka.of_floats(q, k, v, do, causal))
 
 
 def test_attn_spiked_softmax_branch():
@@ -79,3 +84,4 @@ def test_attn_spiked_softmax_branch():
                        v.bfloat16().to(dev()), True)
     err = (og.float().cpu() - o_ref).abs().max().item()
     assert err < 0.05, f"spiked forward max err {err}"
+    ka.check("attention.spiked.o", og, ka.of_floats(q, k, v, None, True)["o"])
