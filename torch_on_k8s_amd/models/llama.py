@@ -6,7 +6,9 @@ metric). Design choices for MI355X:
 
   * bf16 weights/activations end-to-end; fp32 accumulation inside the
     fused HIP ops (RMSNorm, RoPE, flash attention, AdamW).
-  * Plain projection GEMMs go through hipBLASLt/rocBLAS via torch.matmul;
+  * Projections go through ops.linear: forward and dgrad are
+    hipBLASLt/rocBLAS calls, the weight gradient is the gfx950 kernel of
+    ops/csrc/wgrad_gemm.hip, accumulated straight into the flat grads;
     everything fusable is a handwritten gfx950 kernel in ops/.
   * RoPE cos/sin tables precomputed on host (fp32) -- no device trig.
   * 288 GB HBM3E per GPU: default training config holds the whole model,
@@ -111,7 +113,7 @@ class Attention(nn.Module):
     def project_qkv(self, x, cos, sin):
         """Packed projection -> roped contiguous q, k, v."""
         cfg = self.cfg
-        qkv = self.qkv_proj(x)
+        qkv = ops.linear(x, self.qkv_proj.weight)
         return ops.qkv_rope(qkv, cos, sin, cfg.num_heads, cfg.num_kv_heads,
                             cfg.head_dim)
 
@@ -128,7 +130,8 @@ class Attention(nn.Module):
             o = o.transpose(1, 2).contiguous()
         else:
             o = ops.attention(q, k, v, causal=True)
-        return self.o_proj(o.reshape(B, S, cfg.num_heads * cfg.head_dim))
+        return ops.linear(o.reshape(B, S, cfg.num_heads * cfg.head_dim),
+                          self.o_proj.weight)
 
 
 class MLP(nn.Module):
@@ -143,7 +146,8 @@ class MLP(nn.Module):
         self.down_proj = nn.Linear(cfg.intermediate_size, cfg.hidden_size, bias=False)
 
     def forward(self, x):
-        return self.down_proj(ops.swiglu(self.gate_up_proj(x)))
+        gu = ops.linear(x, self.gate_up_proj.weight)
+        return ops.linear(ops.swiglu(gu), self.down_proj.weight)
 
 
 class Block(nn.Module):
@@ -225,7 +229,7 @@ class LlamaModel(nn.Module):
     def forward(self, input_ids: torch.Tensor,
                 labels: torch.Tensor | None = None):
         x = self.forward_hidden(input_ids)
-        logits = self.lm_head(x)
+        logits = ops.linear(x, self.lm_head.weight)
         if labels is None:
             return logits
         return ops.cross_entropy(logits, labels)

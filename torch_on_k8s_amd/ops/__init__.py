@@ -15,6 +15,8 @@ container, built MI355X-first per SURVEY.md §7 step 2.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 try:  # the in-tree gfx950 extension; built by `setup.py build_ext --inplace`
@@ -699,7 +701,156 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         logits.float().view(-1, logits.shape[-1]), labels.reshape(-1))
 
 
+# --------------------------------------------------------------------------
+# Weight-gradient GEMM and the linear layer that accumulates through it
+# --------------------------------------------------------------------------
+_WGRAD_TILE = 256      # output tile edge of wgrad_gemm_kernel
+_WGRAD_TOKENS = 64     # tokens per step
+_WGRAD_GROUP = 4       # raster band height, in dy column slabs
+
+# Dispatch by output shape [N, K], from tools/bench_wgrad.py at 32768 tokens
+# (profiles/wgrad_gemm.log). The kernel serves a shape only where it was
+# measured and its slowest round beat the fastest round of the library's
+# mm + add_; the value is the fastest raster band height. "blas": the
+# library won. A shape that is not listed was not measured and stays on the
+# library (a small output is a handful of blocks on 256 CUs).
+_WGRAD_DISPATCH = {
+    (28672, 4096): 4,        # gate_up  5.82-5.84 ms against 6.43-6.58
+    (4096, 14336): 4,        # down     3.35-3.37 against 3.80-3.83
+    (4096, 4096): 8,         # o        0.82-0.84 against 0.91-0.97
+    (128256, 4096): 4,       # lm_head  27.96-27.99 against 29.94-30.10
+    (6144, 4096): "blas",    # qkv      1.51-1.53 against 1.41-1.51
+}
+
+
+def wgrad_impl() -> str:
+    """TOK_WGRAD_IMPL, read at every call so one process can run an A/B:
+    'hip' (default): the kernel for the shapes the dispatch table gives it;
+    'hip_all': the kernel wherever it can run (tests, measuring new shapes);
+    'blas': the library everywhere, and ops.linear is plain F.linear."""
+    impl = os.environ.get("TOK_WGRAD_IMPL", "hip").lower()
+    if impl not in ("hip", "hip_all", "blas"):
+        raise ValueError(
+            f"TOK_WGRAD_IMPL must be hip, hip_all or blas, got {impl!r}")
+    return impl
+
+
+def wgrad_band(N: int, K: int) -> int | None:
+    """Raster band height if the current TOK_WGRAD_IMPL sends an [N, K]
+    output to the kernel, None if it goes to the library."""
+    impl = wgrad_impl()
+    band = _WGRAD_DISPATCH.get((N, K))
+    if impl == "hip_all":
+        return band if isinstance(band, int) else _WGRAD_GROUP
+    if impl == "hip" and isinstance(band, int):
+        return band
+    return None
+
+
+def wgrad_fast_path(dy: torch.Tensor, x: torch.Tensor,
+                    out: torch.Tensor) -> bool:
+    """True if wgrad_gemm_kernel can run on these operands (whether it is
+    chosen is wgrad_band's business)."""
+    if not (dy.is_cuda and x.is_cuda and out.is_cuda):
+        return False
+    if dy.dim() != 2 or x.dim() != 2 or out.dim() != 2:
+        return False
+    M, N = dy.shape
+    K = x.shape[1]
+    return (all(t.dtype == torch.bfloat16 and t.is_contiguous() and
+                t.data_ptr() % 16 == 0 for t in (dy, x, out))
+            and M >= _WGRAD_TOKENS and M % _WGRAD_TOKENS == 0
+            and N >= _WGRAD_TILE and N % _WGRAD_TILE == 0
+            and K >= _WGRAD_TILE and K % _WGRAD_TILE == 0)
+
+
+@torch.no_grad()
+def wgrad_gemm_(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor,
+                accumulate: bool, *, group: int | None = None) -> torch.Tensor:
+    """out[N,K] = (out if accumulate else 0) + dy[M,N]^T @ x[M,K], in place.
+
+    CUDA bf16, contiguous, 16-byte aligned operands with M % 64 == 0 and N, K
+    multiples of 256 run wgrad_gemm_kernel: fp32 accumulation, the old `out`
+    added in fp32, one rounding, no temporary, where wgrad_band() gives the
+    shape to the kernel (or `group` is passed, which forces it). It launches
+    on the current stream and neither allocates nor syncs, so it can be
+    captured. Every other input computes torch.mm(dy.t(), x) and adds or
+    copies it. A GPU call the kernel should serve raises if the extension
+    is not built, as every op of this package does."""
+    if x.shape[0] != dy.shape[0] or out.shape != (dy.shape[1], x.shape[1]):
+        raise ValueError(
+            f"wgrad_gemm_: dy {tuple(dy.shape)}, x {tuple(x.shape)}, "
+            f"out {tuple(out.shape)} do not fit out[N,K] = dy[M,N]^T x[M,K]")
+    if group is None:
+        group = wgrad_band(*out.shape)
+    if group is not None and wgrad_fast_path(dy, x, out):
+        _require_ext("wgrad_gemm_").wgrad_gemm_(
+            dy, x, out, bool(accumulate), int(group))
+        return out
+    g = torch.mm(dy.t(), x)
+    if accumulate:
+        out.add_(g)
+    else:
+        out.copy_(g)
+    return out
+
+
+def _grad_in_place(weight: torch.Tensor) -> bool:
+    """The weight's .grad is a flat-bucket view that nothing watches, so
+    backward may add into it and hand autograd None: no post-accumulate hook
+    and no tensor hook (register_hook) waits for this gradient. Both hook
+    tables are private attributes of torch.Tensor; test_kernel_oracle_gemm
+    fails if either is renamed. Restriction that stays: such a weight gets
+    no gradient from torch.autograd.grad(), which never touches .grad;
+    FlatBucketModel sets the mark and trains through backward() only."""
+    return (getattr(weight, "_tok_flat_grad", False)
+            and weight.grad is not None
+            and not getattr(weight, "_post_accumulate_grad_hooks", None)
+            and not getattr(weight, "_backward_hooks", None))
+
+
+class _LinearFn(torch.autograd.Function):
+    """y = x @ W^T. Forward and dx are the library calls nn.Linear makes;
+    dW goes through wgrad_gemm_, straight into W.grad where that is a
+    flat-bucket view without hooks (returning None to autograd), into a
+    fresh tensor otherwise."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        ctx.param = weight      # the Parameter itself: .grad and its marks
+        return torch.nn.functional.linear(x, weight)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        param = ctx.param
+        N, K = weight.shape
+        dx = dw = None
+        dy2 = dy.reshape(-1, N)
+        if ctx.needs_input_grad[0]:
+            dx = dy2.mm(weight).view(x.shape)
+        if ctx.needs_input_grad[1]:
+            dy2 = dy2.contiguous()
+            x2 = x.reshape(-1, K).contiguous()
+            if _grad_in_place(param) and param.grad.dtype == dy2.dtype:
+                wgrad_gemm_(dy2, x2, param.grad, True)
+            else:
+                dw = wgrad_gemm_(dy2, x2, torch.empty_like(weight), False)
+        return dx, dw
+
+
+def linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """Bias-free linear layer over the last dimension of x. With
+    TOK_WGRAD_IMPL=blas it is torch.nn.functional.linear under plain
+    autograd."""
+    if wgrad_impl() == "blas":
+        return torch.nn.functional.linear(x, weight)
+    return _LinearFn.apply(x, weight)
+
+
 __all__ = [
+    "linear", "wgrad_gemm_", "wgrad_fast_path", "wgrad_impl", "wgrad_band",
     "rmsnorm", "rmsnorm_ref", "apply_rope", "rope_ref", "fused_adamw_",
     "attention", "attention_ref", "cross_entropy", "layernorm",
     "qkv_rope", "qkv_rope_ref", "swiglu", "swiglu_ref",

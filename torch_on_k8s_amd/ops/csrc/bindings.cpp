@@ -46,6 +46,9 @@ hipError_t tok_adamw(void* p, const void* g, float* m, float* v, long n,
                      int step, float gscale, const int* step_dev,
                      const float* lr_dev, const float* gscale_dev,
                      hipStream_t stream);
+hipError_t tok_wgrad_gemm(const void* dy, const void* x, void* c, long M,
+                          long N, long K, int accumulate, int group,
+                          hipStream_t stream);
 int tok_grad_sumsq_max_blocks();
 int tok_grad_sumsq_blocks(long n);
 hipError_t tok_grad_sumsq(const void* g, long n, float* partials, int nblocks,
@@ -677,6 +680,31 @@ at::Tensor mfma_probe(at::Tensor A, at::Tensor B) {
 
 }  // namespace
 
+// out[N,K] (+)= dy[M,N]^T x[M,K] by the hand kernel. The caller (ops.
+// wgrad_gemm_) has checked the shape rules; this re-checks what would
+// otherwise read or write out of bounds. Allocates nothing, does not sync.
+void wgrad_gemm_(at::Tensor dy, at::Tensor x, at::Tensor out, bool accumulate,
+                 int64_t group) {
+  CHECK_BF16_CUDA(dy);
+  CHECK_BF16_CUDA(x);
+  CHECK_BF16_CUDA(out);
+  TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && out.dim() == 2,
+              "wgrad_gemm_: dy, x and out must be 2-D");
+  const long M = dy.size(0), N = dy.size(1), K = x.size(1);
+  TORCH_CHECK(x.size(0) == M && out.size(0) == N && out.size(1) == K,
+              "wgrad_gemm_: need dy [M,N], x [M,K], out [N,K]");
+  TORCH_CHECK(M >= 64 && M % 64 == 0 && N >= 256 && N % 256 == 0 &&
+                  K >= 256 && K % 256 == 0,
+              "wgrad_gemm_: needs M % 64 == 0 and N, K multiples of 256");
+  TORCH_CHECK(((uintptr_t)dy.data_ptr() | (uintptr_t)x.data_ptr() |
+               (uintptr_t)out.data_ptr()) % 16 == 0,
+              "wgrad_gemm_: pointers must be 16-byte aligned");
+  TORCH_CHECK(group >= 1, "wgrad_gemm_: group must be >= 1");
+  TOK_HIP_OK(tok_wgrad_gemm(dy.data_ptr(), x.data_ptr(), out.data_ptr(), M, N,
+                            K, accumulate ? 1 : 0, (int)group,
+                            current_stream()));
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("mfma_probe", &mfma_probe, "MFMA 16x16x32 bf16 layout probe");
   mod.def("attn_fwd", &attn_fwd, "Flash attention forward (bf16, gfx950)",
@@ -739,4 +767,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "Sum partials -> {norm, clip-folded grad scale} (gfx950)",
           py::arg("partials"), py::arg("out"), py::arg("inv_count"),
           py::arg("clip"));
+  mod.def("wgrad_gemm_", &wgrad_gemm_,
+          "out[N,K] (+)= dy[M,N]^T x[M,K], bf16, fp32 accumulate (gfx950)",
+          py::arg("dy"), py::arg("x"), py::arg("out"), py::arg("accumulate"),
+          py::arg("group"));
 }

@@ -110,6 +110,9 @@ class FlatBucketModel:
                     .view(s.param.shape)
                 s.param.grad = b.flat_grad[s.offset:s.offset + s.numel] \
                     .view(s.param.shape)
+                # ops.linear accumulates its weight gradient straight into
+                # such a view when no post-accumulate hook is registered
+                s.param._tok_flat_grad = True
             b.pending = len(b.segs)
 
         # gradient accumulation: while True, backward only accumulates
