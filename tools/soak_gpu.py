@@ -44,6 +44,9 @@ def main():
     mem_marks = {}
     writer = None
     snapshots = 0
+    # the early mark: step 20, or the last step of a shorter run, so that a
+    # short run still gets as far as printing the peak
+    mark = min(20, args.steps - 1)
     for i in range(args.steps):
         loss = float(tr.train_step())
         assert loss == loss and abs(loss) < 1e4, f"loss blew up: {loss}"
@@ -52,21 +55,22 @@ def main():
                 (writer is None or not writer.is_alive()):
             writer = tr.snapshot_checkpoint_async(args.ckpt_dir)
             snapshots += 1
-        if i in (20, args.steps - 1):
+        if i in (mark, args.steps - 1):
             torch.cuda.synchronize()
             mem_marks[i] = torch.cuda.memory_allocated()
     if writer is not None:
         writer.join(timeout=600)
         # the published checkpoint must resume
         tr.load_checkpoint(args.ckpt_dir)
-    first = sum(losses[:10]) / 10
-    last = sum(losses[-10:]) / 10
-    growth = mem_marks[args.steps - 1] - mem_marks[20]
+    win = max(1, min(10, args.steps // 2))
+    first = sum(losses[:win]) / win
+    last = sum(losses[-win:]) / win
+    growth = mem_marks[args.steps - 1] - mem_marks[mark]
     out = {
         "steps": args.steps,
         "loss_first10": round(first, 4),
         "loss_last10": round(last, 4),
-        "mem_at_20_gb": round(mem_marks[20] / 2**30, 2),
+        "mem_at_20_gb": round(mem_marks[mark] / 2**30, 2),
         "mem_at_end_gb": round(mem_marks[args.steps - 1] / 2**30, 2),
         "mem_growth_mb": round(growth / 2**20, 2),
         "max_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 2),

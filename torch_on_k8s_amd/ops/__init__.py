@@ -809,9 +809,117 @@ def _grad_in_place(weight: torch.Tensor) -> bool:
             and not getattr(weight, "_backward_hooks", None))
 
 
+# --------------------------------------------------------------------------
+# Input-gradient GEMM: dx = dy @ W as a TN call on a transposed weight copy
+# --------------------------------------------------------------------------
+_TRANSPOSE_TILE = 64           # tile edge of weight_transpose_kernel
+_TRANSPOSE_MAX_ROWS = 65535 * _TRANSPOSE_TILE    # grid.y limit
+
+
+def _transpose_contract(src: torch.Tensor, out: torch.Tensor) -> str | None:
+    """What of transpose_2d_'s contract the operands break, None if nothing."""
+    if src.dim() != 2 or out.dim() != 2:
+        return "src and out must be 2-D"
+    if src.dtype != torch.bfloat16 or out.dtype != torch.bfloat16:
+        return f"src and out must be bfloat16, got {src.dtype}, {out.dtype}"
+    if src.device != out.device:
+        return "src and out must be on one device"
+    R, C = src.shape
+    if tuple(out.shape) != (C, R):
+        return f"out must be {(C, R)}, got {tuple(out.shape)}"
+    if R < 8 or C < 8 or R % 8 or C % 8:
+        return f"R and C must be multiples of 8, got {R}, {C}"
+    if R > _TRANSPOSE_MAX_ROWS:
+        return f"R must not exceed {_TRANSPOSE_MAX_ROWS}"
+    if not (src.is_contiguous() and out.is_contiguous()):
+        return "src and out must be contiguous"
+    a, b = src.data_ptr(), out.data_ptr()
+    if a % 16 or b % 16:
+        return "src and out must be 16-byte aligned"
+    nbytes = R * C * 2
+    if a < b + nbytes and b < a + nbytes:
+        return "src and out must not overlap"
+    return None
+
+
+@torch.no_grad()
+def transpose_2d_(src: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out[C,R] = src[R,C]^T for bf16, row-major, contiguous, 16-byte
+    aligned, non-overlapping tensors with R and C multiples of 8; anything
+    else raises ValueError. Bit patterns are moved, not numbers. On the GPU
+    it is one launch of weight_transpose_kernel on the current stream, which
+    neither allocates nor syncs, so it can be captured; CPU tensors do
+    out.copy_(src.t())."""
+    why = _transpose_contract(src, out)
+    if why is not None:
+        raise ValueError(f"transpose_2d_: {why}")
+    if src.is_cuda:
+        _require_ext("transpose_2d_").transpose_2d_(src, out)
+    else:
+        out.copy_(src.t())
+    return out
+
+
+# Dispatch by weight shape [N, K], from tools/bench_dgrad.py at 32768 tokens
+# (profiles/dgrad_wt.log): (a) the library's NN call dy.mm(W) against (d) the
+# transposition followed by the TN call F.linear(dy, Wt), fastest-slowest
+# round in ms. A shape takes the transposed path only where the slowest round
+# of (d) beat the fastest round of (a). A shape that is not listed was not
+# measured and stays on dy.mm(W).
+_DGRAD_DISPATCH = {
+    (28672, 4096): True,     # gate_up  (d) 5.11-5.12 against (a) 5.54-6.16
+    (4096, 14336): True,     # down     2.49-2.52 against 2.89-3.05
+    (6144, 4096): True,      # qkv      1.08-1.11 against 1.23-1.28
+    (4096, 4096): True,      # o        0.72-0.75 against 0.85-0.90
+    (128256, 4096): True,    # lm_head  22.32-22.38 against 25.82-25.91
+}
+
+
+def dgrad_impl() -> str:
+    """TOK_DGRAD_IMPL, read at every call so one process can run an A/B:
+    'wt' (default): the transposed path for the shapes the table gives it;
+    'wt_all': the transposed path wherever transpose_2d_ can run (tests,
+    measuring new shapes); 'blas': dy.mm(W) everywhere. Independent of
+    TOK_WGRAD_IMPL, except that with TOK_WGRAD_IMPL=blas ops.linear is plain
+    F.linear and never gets here."""
+    impl = os.environ.get("TOK_DGRAD_IMPL", "wt").lower()
+    if impl not in ("wt", "wt_all", "blas"):
+        raise ValueError(
+            f"TOK_DGRAD_IMPL must be wt, wt_all or blas, got {impl!r}")
+    return impl
+
+
+def dgrad_transposed(N: int, K: int) -> bool:
+    """True if the current TOK_DGRAD_IMPL sends the dgrad of an [N, K]
+    weight through the transposed copy."""
+    impl = dgrad_impl()
+    if impl == "wt_all":
+        return True
+    return impl == "wt" and _DGRAD_DISPATCH.get((N, K)) is True
+
+
+def dgrad(dy2: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """dx[M,K] = dy2[M,N] @ weight[N,K]. Where dgrad_transposed() says so and
+    the weight fits transpose_2d_'s contract on the GPU: Wt = weight^T into a
+    temporary made in this call from the live weight (so it cannot be stale;
+    under capture it comes from the graph's private pool), then the TN call
+    F.linear(dy2, Wt). Everything else is dy2.mm(weight)."""
+    N, K = weight.shape
+    if (weight.is_cuda and weight.dtype == torch.bfloat16
+            and dy2.dtype == torch.bfloat16 and weight.is_contiguous()
+            and weight.data_ptr() % 16 == 0 and N % 8 == 0 and K % 8 == 0
+            and 8 <= N <= _TRANSPOSE_MAX_ROWS and K >= 8
+            and dgrad_transposed(N, K)):
+        wt = torch.empty((K, N), dtype=weight.dtype, device=weight.device)
+        transpose_2d_(weight, wt)
+        return torch.nn.functional.linear(dy2, wt)
+    return dy2.mm(weight)
+
+
 class _LinearFn(torch.autograd.Function):
-    """y = x @ W^T. Forward and dx are the library calls nn.Linear makes;
-    dW goes through wgrad_gemm_, straight into W.grad where that is a
+    """y = x @ W^T. Forward is the library call nn.Linear makes; dx goes
+    through dgrad (the same library, in the layout it is fastest at); dW
+    goes through wgrad_gemm_, straight into W.grad where that is a
     flat-bucket view without hooks (returning None to autograd), into a
     fresh tensor otherwise."""
 
@@ -829,7 +937,7 @@ class _LinearFn(torch.autograd.Function):
         dx = dw = None
         dy2 = dy.reshape(-1, N)
         if ctx.needs_input_grad[0]:
-            dx = dy2.mm(weight).view(x.shape)
+            dx = dgrad(dy2, weight).view(x.shape)
         if ctx.needs_input_grad[1]:
             dy2 = dy2.contiguous()
             x2 = x.reshape(-1, K).contiguous()
@@ -851,6 +959,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
 
 __all__ = [
     "linear", "wgrad_gemm_", "wgrad_fast_path", "wgrad_impl", "wgrad_band",
+    "dgrad", "dgrad_impl", "dgrad_transposed", "transpose_2d_",
     "rmsnorm", "rmsnorm_ref", "apply_rope", "rope_ref", "fused_adamw_",
     "attention", "attention_ref", "cross_entropy", "layernorm",
     "qkv_rope", "qkv_rope_ref", "swiglu", "swiglu_ref",

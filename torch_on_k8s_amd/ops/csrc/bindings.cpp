@@ -73,6 +73,8 @@ hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
                         int dq_variant);
 hipError_t tok_transpose_head(const void* in, void* out, int B, int S, int H,
                               int D, int S_pad, hipStream_t stream);
+hipError_t tok_transpose_2d(const void* in, void* out, long R, long C,
+                            hipStream_t stream);
 hipError_t tok_attn_decode(const void* q, const void* k, const void* v,
                            void* out, int B, int T, const int* T_dev,
                            int Tmax, int Hq, int Hkv, int D,
@@ -705,6 +707,31 @@ void wgrad_gemm_(at::Tensor dy, at::Tensor x, at::Tensor out, bool accumulate,
                             current_stream()));
 }
 
+// out[C,R] = in[R,C]^T, bf16 bit patterns, by weight_transpose_kernel. The
+// caller (ops.transpose_2d_) has checked the contract and raises ValueError;
+// this re-checks what would otherwise read or write out of bounds. One
+// launch on the current stream, no allocation, no sync.
+void transpose_2d_(at::Tensor in, at::Tensor out) {
+  CHECK_BF16_CUDA(in);
+  CHECK_BF16_CUDA(out);
+  TORCH_CHECK(in.dim() == 2 && out.dim() == 2 &&
+                  out.size(0) == in.size(1) && out.size(1) == in.size(0),
+              "transpose_2d_: need in [R,C] and out [C,R]");
+  TORCH_CHECK(in.get_device() == out.get_device(),
+              "transpose_2d_: in and out must be on one device");
+  const long R = in.size(0), C = in.size(1);
+  TORCH_CHECK(R >= 8 && C >= 8 && R % 8 == 0 && C % 8 == 0,
+              "transpose_2d_: R and C must be multiples of 8");
+  const uintptr_t a = (uintptr_t)in.data_ptr(), b = (uintptr_t)out.data_ptr();
+  TORCH_CHECK((a | b) % 16 == 0,
+              "transpose_2d_: pointers must be 16-byte aligned");
+  const uintptr_t bytes = (uintptr_t)R * C * 2;
+  TORCH_CHECK(a + bytes <= b || b + bytes <= a,
+              "transpose_2d_: in and out must not overlap");
+  TOK_HIP_OK(tok_transpose_2d(in.data_ptr(), out.data_ptr(), R, C,
+                              current_stream()));
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("mfma_probe", &mfma_probe, "MFMA 16x16x32 bf16 layout probe");
   mod.def("attn_fwd", &attn_fwd, "Flash attention forward (bf16, gfx950)",
@@ -771,4 +798,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "out[N,K] (+)= dy[M,N]^T x[M,K], bf16, fp32 accumulate (gfx950)",
           py::arg("dy"), py::arg("x"), py::arg("out"), py::arg("accumulate"),
           py::arg("group"));
+  mod.def("transpose_2d_", &transpose_2d_,
+          "out[C,R] = in[R,C]^T, bf16 bit patterns (gfx950)",
+          py::arg("src"), py::arg("out"));
 }
