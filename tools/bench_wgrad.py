@@ -7,8 +7,14 @@ Operands are randn scaled like activations and gradients: zero-filled
 operands read 15-20 % high on an MFMA-dense kernel. For reference the TN
 (forward) and NN (dgrad) library calls of the same FLOPs are timed too.
 
+Arms: hip_g<G> is the incumbent schedule (variant 0, no half blocks) at band
+height G; v1_g<G> variant 1; v0s_g<G> and v1s_g<G> the same two with the
+trailing tiles as half blocks by the rule of ops.wgrad_split (equal to the
+arm without "s" where the rule gives 0).
+
     python tools/bench_wgrad.py [--rounds 3] [--iters 5] [--tokens 32768]
                                 [--shapes gate_up,down,...] [--groups 1,4,8]
+                                [--vgroups 4,8] [--no-blas]
 """
 from __future__ import annotations
 
@@ -49,9 +55,14 @@ def main():
     ap.add_argument("--tokens", type=int, default=32768)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--groups", default="1,4,8")
+    ap.add_argument("--vgroups", default="4,8",
+                    help="band heights of the variant x split arms")
+    ap.add_argument("--no-blas", action="store_true",
+                    help="kernel arms only (counter runs)")
     args = ap.parse_args()
     M = args.tokens
     groups = [int(g) for g in args.groups.split(",")]
+    vgroups = [int(g) for g in args.vgroups.split(",") if g]
     dev = torch.device("cuda", 0)
     print(f"# {torch.cuda.get_device_name(0)} tokens={M} rounds={args.rounds} "
           f"iters={args.iters}")
@@ -93,14 +104,23 @@ def main():
             s = i % nset
             torch.mm(dys[s], ws[s])
 
-        arms = {"blas_nt+add": lib_nt, "blas_nt": lib_nt_mm_only,
-                "blas_tn": lib_tn, "blas_nn": lib_nn}
-        for g in groups:
+        arms = {} if args.no_blas else {
+            "blas_nt+add": lib_nt, "blas_nt": lib_nt_mm_only,
+            "blas_tn": lib_tn, "blas_nn": lib_nn}
+
+        def hip(g, variant, split):
             # the extension directly: ops.wgrad_gemm_ would apply the
             # dispatch table this tool exists to fill
-            arms[f"hip_g{g}"] = (
-                lambda i, g=g: ops._C.wgrad_gemm_(dys[i % nset], xs[i % nset],
-                                                  gs[i % nset], True, g))
+            return lambda i: ops._C.wgrad_gemm_(
+                dys[i % nset], xs[i % nset], gs[i % nset], True, g, variant,
+                split)
+
+        for g in groups:
+            arms[f"hip_g{g}"] = hip(g, 0, 0)
+        for g in vgroups:
+            arms[f"v1_g{g}"] = hip(g, 1, 0)
+            arms[f"v0s_g{g}"] = hip(g, 0, -1)
+            arms[f"v1s_g{g}"] = hip(g, 1, -1)
         for fn in arms.values():              # warm-up: kernel selection
             fn(0)
         torch.cuda.synchronize()

@@ -709,17 +709,19 @@ _WGRAD_TOKENS = 64     # tokens per step
 _WGRAD_GROUP = 4       # raster band height, in dy column slabs
 
 # Dispatch by output shape [N, K], from tools/bench_wgrad.py at 32768 tokens
-# (profiles/wgrad_gemm.log). The kernel serves a shape only where it was
-# measured and its slowest round beat the fastest round of the library's
-# mm + add_; the value is the fastest raster band height. "blas": the
-# library won. A shape that is not listed was not measured and stays on the
-# library (a small output is a handful of blocks on 256 CUs).
+# (profiles/wgrad_gemm.log for the first kernel, profiles/wgrad_v2.log for
+# variant 1 and the half blocks, whose figures stand below). The kernel
+# serves a shape only where it was measured and its slowest round beat the
+# fastest round of the library's mm + add_; the value is the raster band
+# height. "blas": the library won when the table was made. A shape that is
+# not listed was not measured and stays on the library (a small output is a
+# handful of blocks on 256 CUs).
 _WGRAD_DISPATCH = {
-    (28672, 4096): 4,        # gate_up  5.82-5.84 ms against 6.43-6.58
-    (4096, 14336): 4,        # down     3.35-3.37 against 3.80-3.83
-    (4096, 4096): 8,         # o        0.82-0.84 against 0.91-0.97
-    (128256, 4096): 4,       # lm_head  27.96-27.99 against 29.94-30.10
-    (6144, 4096): "blas",    # qkv      1.51-1.53 against 1.41-1.51
+    (28672, 4096): 4,        # gate_up  5.68-5.71 ms against 6.76-6.81
+    (4096, 14336): 4,        # down     2.95-2.98 (128 tiles halved) / 3.91-3.92
+    (4096, 4096): 8,         # o        0.79-0.81 against 1.00-1.01
+    (128256, 4096): 4,       # lm_head  26.53-26.63 (80 halved) / 30.80-30.98
+    (6144, 4096): "blas",    # qkv      kept: now 1.26-1.29 against 1.51-1.52
 }
 
 
@@ -764,9 +766,38 @@ def wgrad_fast_path(dy: torch.Tensor, x: torch.Tensor,
             and K >= _WGRAD_TILE and K % _WGRAD_TILE == 0)
 
 
+def wgrad_variant() -> int:
+    """TOK_WGRAD_VARIANT, read at every call so one process can ablate the
+    kernel's schedule: 0 is the two-barrier schedule, 1 reads the LDS
+    fragments under the MFMAs; unset (or negative) is the extension's
+    default. Every variant gives the same bits."""
+    raw = os.environ.get("TOK_WGRAD_VARIANT", "-1")
+    try:
+        v = int(raw)
+    except ValueError:
+        v = 2
+    if v > 1:
+        raise ValueError(f"TOK_WGRAD_VARIANT must be 0 or 1, got {raw!r}")
+    return max(v, -1)
+
+
+def wgrad_split(N: int, K: int, cus: int) -> int:
+    """Trailing tiles of an [N, K] output that wgrad_gemm_ computes as two
+    128 x 256 half blocks each on a device of `cus` compute units. One block
+    runs per unit, so r = tiles % cus tiles are left for the last round;
+    when their 2 r halves still fit one round (0 < 2 r <= cus) that round
+    costs a half block's time instead of a full one's."""
+    if N <= 0 or K <= 0 or cus <= 0:
+        return 0
+    r = ((N // _WGRAD_TILE) * (K // _WGRAD_TILE)) % cus
+    return r if 0 < 2 * r <= cus else 0
+
+
 @torch.no_grad()
 def wgrad_gemm_(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor,
-                accumulate: bool, *, group: int | None = None) -> torch.Tensor:
+                accumulate: bool, *, group: int | None = None,
+                variant: int | None = None,
+                split: int | None = None) -> torch.Tensor:
     """out[N,K] = (out if accumulate else 0) + dy[M,N]^T @ x[M,K], in place.
 
     CUDA bf16, contiguous, 16-byte aligned operands with M % 64 == 0 and N, K
@@ -774,7 +805,10 @@ def wgrad_gemm_(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor,
     added in fp32, one rounding, no temporary, where wgrad_band() gives the
     shape to the kernel (or `group` is passed, which forces it). It launches
     on the current stream and neither allocates nor syncs, so it can be
-    captured. Every other input computes torch.mm(dy.t(), x) and adds or
+    captured. `variant` picks the kernel's schedule (None: wgrad_variant());
+    `split` the number of trailing tiles computed as half blocks (None: the
+    rule of wgrad_split for the device, 0: none). Neither changes a bit of
+    the result. Every other input computes torch.mm(dy.t(), x) and adds or
     copies it. A GPU call the kernel should serve raises if the extension
     is not built, as every op of this package does."""
     if x.shape[0] != dy.shape[0] or out.shape != (dy.shape[1], x.shape[1]):
@@ -784,8 +818,16 @@ def wgrad_gemm_(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor,
     if group is None:
         group = wgrad_band(*out.shape)
     if group is not None and wgrad_fast_path(dy, x, out):
+        tiles = (out.shape[0] // _WGRAD_TILE) * (out.shape[1] // _WGRAD_TILE)
+        if split is not None and not 0 <= split <= tiles:
+            raise ValueError(
+                f"wgrad_gemm_: split {split} outside 0..{tiles} tiles")
+        if variant is not None and variant not in (0, 1):
+            raise ValueError(f"wgrad_gemm_: variant {variant} is not 0 or 1")
         _require_ext("wgrad_gemm_").wgrad_gemm_(
-            dy, x, out, bool(accumulate), int(group))
+            dy, x, out, bool(accumulate), int(group),
+            wgrad_variant() if variant is None else int(variant),
+            -1 if split is None else int(split))
         return out
     g = torch.mm(dy.t(), x)
     if accumulate:
@@ -959,6 +1001,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
 
 __all__ = [
     "linear", "wgrad_gemm_", "wgrad_fast_path", "wgrad_impl", "wgrad_band",
+    "wgrad_variant", "wgrad_split",
     "dgrad", "dgrad_impl", "dgrad_transposed", "transpose_2d_",
     "rmsnorm", "rmsnorm_ref", "apply_rope", "rope_ref", "fused_adamw_",
     "attention", "attention_ref", "cross_entropy", "layernorm",

@@ -48,7 +48,10 @@ hipError_t tok_adamw(void* p, const void* g, float* m, float* v, long n,
                      hipStream_t stream);
 hipError_t tok_wgrad_gemm(const void* dy, const void* x, void* c, long M,
                           long N, long K, int accumulate, int group,
-                          hipStream_t stream);
+                          int variant, long split, hipStream_t stream);
+long tok_wgrad_split(long tiles, long cus);
+hipError_t tok_wgrad_cus(int* cus);
+int tok_wgrad_default_variant();
 int tok_grad_sumsq_max_blocks();
 int tok_grad_sumsq_blocks(long n);
 hipError_t tok_grad_sumsq(const void* g, long n, float* partials, int nblocks,
@@ -685,8 +688,10 @@ at::Tensor mfma_probe(at::Tensor A, at::Tensor B) {
 // out[N,K] (+)= dy[M,N]^T x[M,K] by the hand kernel. The caller (ops.
 // wgrad_gemm_) has checked the shape rules; this re-checks what would
 // otherwise read or write out of bounds. Allocates nothing, does not sync.
+// `variant` < 0: the default schedule; `split` < 0: the rule for the device's
+// compute units (wgrad_split). Every choice gives the same bits.
 void wgrad_gemm_(at::Tensor dy, at::Tensor x, at::Tensor out, bool accumulate,
-                 int64_t group) {
+                 int64_t group, int64_t variant, int64_t split) {
   CHECK_BF16_CUDA(dy);
   CHECK_BF16_CUDA(x);
   CHECK_BF16_CUDA(out);
@@ -702,10 +707,28 @@ void wgrad_gemm_(at::Tensor dy, at::Tensor x, at::Tensor out, bool accumulate,
                (uintptr_t)out.data_ptr()) % 16 == 0,
               "wgrad_gemm_: pointers must be 16-byte aligned");
   TORCH_CHECK(group >= 1, "wgrad_gemm_: group must be >= 1");
+  TORCH_CHECK(variant <= 1, "wgrad_gemm_: variant must be 0, 1 or negative");
+  TORCH_CHECK(split <= (N / 256) * (K / 256),
+              "wgrad_gemm_: split must not exceed the number of tiles");
   TOK_HIP_OK(tok_wgrad_gemm(dy.data_ptr(), x.data_ptr(), out.data_ptr(), M, N,
                             K, accumulate ? 1 : 0, (int)group,
-                            current_stream()));
+                            variant < 0 ? -1 : (int)variant,
+                            split < 0 ? -1L : (long)split, current_stream()));
 }
+
+// The split rule of wgrad_gemm_ for an [N, K] output on `cus` compute units.
+int64_t wgrad_split(int64_t N, int64_t K, int64_t cus) {
+  return tok_wgrad_split((N / 256) * (K / 256), cus);
+}
+
+// Compute units of the current device, as wgrad_gemm_ counts them.
+int64_t wgrad_cus() {
+  int cus = 0;
+  TOK_HIP_OK(tok_wgrad_cus(&cus));
+  return cus;
+}
+
+int64_t wgrad_default_variant() { return tok_wgrad_default_variant(); }
 
 // out[C,R] = in[R,C]^T, bf16 bit patterns, by weight_transpose_kernel. The
 // caller (ops.transpose_2d_) has checked the contract and raises ValueError;
@@ -797,7 +820,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("wgrad_gemm_", &wgrad_gemm_,
           "out[N,K] (+)= dy[M,N]^T x[M,K], bf16, fp32 accumulate (gfx950)",
           py::arg("dy"), py::arg("x"), py::arg("out"), py::arg("accumulate"),
-          py::arg("group"));
+          py::arg("group"), py::arg("variant") = -1, py::arg("split") = -1);
+  mod.def("wgrad_split", &wgrad_split,
+          "Trailing tiles wgrad_gemm_ computes as half blocks",
+          py::arg("N"), py::arg("K"), py::arg("cus"));
+  mod.def("wgrad_cus", &wgrad_cus, "Compute units of the current device");
+  mod.def("wgrad_default_variant", &wgrad_default_variant,
+          "Schedule wgrad_gemm_ runs when variant is negative");
   mod.def("transpose_2d_", &transpose_2d_,
           "out[C,R] = in[R,C]^T, bf16 bit patterns (gfx950)",
           py::arg("src"), py::arg("out"));
