@@ -11,6 +11,14 @@ plain block order): the calls differ only in the dQ kernel, so the
 difference of their times is the difference of the dQ kernels.
 Within-process interleaved rounds (guide §5.4 rule 24). The flagship
 per-layer shape is --B 8; record runs at both --B 2 and --B 8.
+
+--doc-len L[,L...] times packed-document attention instead: documents of L
+tokens packed into every row, the last one short. One process, interleaved
+rounds of (a) the plain causal call, (b) bounds that describe one document
+per row, and one column per L; forward, and forward plus backward. The
+yardstick printed next to the times is the live-tile ratio counted from the
+layout: the share of the causal row's 32x32 (query, key) blocks that still
+hold a visible pair.
 """
 import argparse
 import os
@@ -40,6 +48,67 @@ def time_fn(fn, iters=10, warmup=3):
     return (time.perf_counter() - t0) / iters
 
 
+def doc_layout(S, L):
+    """doc_start, doc_end (int32 [S]) of documents of L tokens, last short."""
+    idx = torch.arange(S, dtype=torch.int32)
+    ds = idx // L * L
+    return ds, torch.clamp(ds + L, max=S)
+
+
+def live_ratio(S, ds):
+    """Share of the causal 32x32 blocks that hold a pair with
+    doc_start[i] <= j <= i."""
+    n = (S + 31) // 32
+    blk = torch.arange(n)
+    first_row = blk * 32
+    last_row = torch.clamp(first_row + 31, max=S - 1)
+    # doc_start is non-decreasing: a block row's smallest bound is its first
+    # row's, and key block c is live iff it ends past that bound
+    lo = ds[first_row].long().view(n, 1)
+    live = (blk.view(1, n) * 32 <= last_row.view(n, 1)) & \
+        (blk.view(1, n) * 32 + 31 >= lo)
+    return float(live.sum()) / (n * (n + 1) // 2)
+
+
+def bench_docs(args, ops, q, k, v, do):
+    B, S = q.shape[:2]
+    dev = q.device
+    cols = [("plain", None)]
+    for L in [S] + [int(x) for x in args.doc_len.split(",")]:
+        ds, de = doc_layout(S, L)
+        name = "one-doc" if L == S else f"doc-len {L}"
+        cols.append((name, (ds, de)))
+    fns, ratios = [], []
+    for name, bd in cols:
+        if bd is None:
+            ratios.append(1.0)
+            fwd = lambda: ops._C.attn_fwd(q, k, v, True)
+            o, lse = fwd()
+            bwd = lambda o=o, lse=lse: ops._C.attn_bwd(q, k, v, o, lse, do,
+                                                       True)
+        else:
+            ratios.append(live_ratio(S, bd[0]))
+            ds = bd[0].to(dev).unsqueeze(0).expand(B, S).contiguous()
+            de = bd[1].to(dev).unsqueeze(0).expand(B, S).contiguous()
+            fwd = lambda ds=ds: ops._C.attn_fwd(q, k, v, True, 0, ds)
+            o, lse = fwd()
+            bwd = lambda o=o, lse=lse, ds=ds, de=de: ops._C.attn_bwd(
+                q, k, v, o, lse, do, True, False, 1, ds, de)
+        fns.append((fwd, bwd, o, lse))
+    o0, lse0 = fns[0][2], fns[0][3]
+    print(f"one-doc bounds vs plain: O bitwise {torch.equal(o0, fns[1][2])}, "
+          f"LSE bitwise {torch.equal(lse0, fns[1][3])}, dQ/dK/dV bitwise "
+          f"{all(torch.equal(a, b) for a, b in zip(fns[0][1](), fns[1][1]()))}")
+    for r in range(args.rounds):
+        tf = [time_fn(f[0], args.iters) for f in fns]
+        tb = [time_fn(f[1], args.iters) for f in fns]
+        for (name, _), ratio, a, b in zip(cols, ratios, tf, tb):
+            print(f"[round {r}] {name:>12}: fwd {a*1e3:7.3f} ms "
+                  f"(x{a/tf[0]:.3f}) | fwd+bwd {(a+b)*1e3:7.3f} ms "
+                  f"(x{(a+b)/(tf[0]+tb[0]):.3f}) | live tiles x{ratio:.3f}",
+                  flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=2)
@@ -53,6 +122,9 @@ def main():
                     help="dQ kernels to time in the fused backward")
     ap.add_argument("--no-sdpa", action="store_true",
                     help="skip the torch SDPA columns (saves time at B=8)")
+    ap.add_argument("--doc-len", default=None,
+                    help="packed documents of this many tokens (comma list):"
+                    " time plain / one document / each length and stop")
     args = ap.parse_args()
     from torch_on_k8s_amd import ops
 
@@ -63,6 +135,9 @@ def main():
     k = torch.randn(B, S, Hkv, D, dtype=torch.bfloat16, device=dev)
     v = torch.randn(B, S, Hkv, D, dtype=torch.bfloat16, device=dev)
     do = torch.randn(B, S, Hq, D, dtype=torch.bfloat16, device=dev)
+    if args.doc_len:
+        bench_docs(args, ops, q, k, v, do)
+        return
     rep = Hq // Hkv
     qt = q.transpose(1, 2).contiguous()
     kt = k.transpose(1, 2).repeat_interleave(rep, dim=1).contiguous()

@@ -16,7 +16,8 @@ from dataclasses import dataclass, field, asdict
 
 import torch
 
-from torch_on_k8s_amd.engine.data import SyntheticTokens
+from torch_on_k8s_amd import ops
+from torch_on_k8s_amd.engine.data import PackedTokenFile, SyntheticTokens
 from torch_on_k8s_amd.models.registry import build_model, get_model_config
 from torch_on_k8s_amd.parallel.ddp import FlatBucketModel, FlatAdamW
 from torch_on_k8s_amd.parallel.env import DistContext
@@ -50,6 +51,11 @@ class TrainerConfig:
     metrics_path: str | None = None  # structured metrics for the elastic
                                      # autoscaler (replaces the reference's
                                      # stdout log-regex, observation.go:40-106)
+    data_path: str | None = None    # flat token file (PackedTokenFile);
+                                    # None = synthetic tokens
+    data_dtype: str = "uint16"      # token width in data_path: uint16|uint32
+    doc_eos_id: int | None = None   # packed documents: attention and RoPE
+                                    # restart after every token with this id
 
     def to_dict(self):
         d = asdict(self)
@@ -86,9 +92,15 @@ class Trainer:
         self.opt = FlatAdamW(
             self.fb, lr=cfg.lr, betas=tuple(cfg.betas),
             weight_decay=cfg.weight_decay)
-        self.data = SyntheticTokens(
-            mcfg.vocab_size, cfg.micro_batch, cfg.seq_len, self.device,
-            rank=ctx.rank, seed=cfg.seed)
+        if cfg.data_path:
+            self.data = PackedTokenFile(
+                cfg.data_path, cfg.data_dtype, cfg.micro_batch, cfg.seq_len,
+                self.device, rank=ctx.rank, world=ctx.world_size,
+                seed=cfg.seed)
+        else:
+            self.data = SyntheticTokens(
+                mcfg.vocab_size, cfg.micro_batch, cfg.seq_len, self.device,
+                rank=ctx.rank, seed=cfg.seed)
         self.step_count = 0
         self._t_last = None
         self._graph = None
@@ -129,6 +141,15 @@ class Trainer:
     def module(self):
         return self.fb.module
 
+    def _loss(self, inp, lab):
+        """Forward of one micro-batch. With doc_eos_id the document bounds
+        are derived from the batch on the device (no host sync, so also
+        inside the captured step) and handed to the model."""
+        if self.cfg.doc_eos_id is None:
+            return self.fb(inp, lab)
+        ds, de = ops.doc_bounds(inp, self.cfg.doc_eos_id)
+        return self.fb(inp, lab, doc_start=ds, doc_end=de)
+
     def train_step(self, sync: bool = True):
         """One full step: data -> fwd -> bwd (overlapped RCCL all-reduce)
         -> optional clip -> fused AdamW.
@@ -147,7 +168,7 @@ class Trainer:
             # final micro-step; earlier ones just accumulate locally
             self.fb.set_accumulate(micro < accum - 1)
             inp, lab = self.data.batch(self.step_count * accum + micro)
-            loss = self.fb(inp, lab)
+            loss = self._loss(inp, lab)
             loss.backward()
         self.fb.finish_grad_sync()
         scale = 1.0 / (self.fb.world_size * accum)
@@ -195,7 +216,7 @@ class Trainer:
             loss = None
             for micro in range(accum):
                 self.fb.set_accumulate(micro < accum - 1)
-                loss = self.fb(inp[micro], lab[micro])
+                loss = self._loss(inp[micro], lab[micro])
                 loss.backward()
             self.fb.finish_grad_sync()
             gscale_dev = None

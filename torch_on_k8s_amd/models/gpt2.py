@@ -129,7 +129,13 @@ class GPT2Model(nn.Module):
                 blk.fc_out.weight.mul_(scale)
 
     def forward(self, input_ids: torch.Tensor,
-                labels: torch.Tensor | None = None):
+                labels: torch.Tensor | None = None,
+                doc_start: torch.Tensor | None = None,
+                doc_end: torch.Tensor | None = None):
+        if doc_start is not None or doc_end is not None:
+            raise NotImplementedError(
+                "GPT-2 has no packed-document path: its learned positions "
+                "do not restart per document")
         B, S = input_ids.shape
         pos = torch.arange(S, device=input_ids.device)
         x = self.wte(input_ids) + self.wpe(pos)

@@ -110,17 +110,23 @@ class Attention(nn.Module):
                                   bias=False)
         self.o_proj = nn.Linear(H * D, cfg.hidden_size, bias=False)
 
-    def project_qkv(self, x, cos, sin):
+    def project_qkv(self, x, cos, sin, doc_start=None):
         """Packed projection -> roped contiguous q, k, v."""
         cfg = self.cfg
         qkv = ops.linear(x, self.qkv_proj.weight)
         return ops.qkv_rope(qkv, cos, sin, cfg.num_heads, cfg.num_kv_heads,
-                            cfg.head_dim)
+                            cfg.head_dim, doc_start=doc_start)
 
-    def forward(self, x, cos, sin):
+    def forward(self, x, cos, sin, doc_start=None, doc_end=None):
+        """doc_start / doc_end: packed-document bounds (ops.doc_bounds);
+        both RoPE positions and the attention mask restart per document."""
         B, S, _ = x.shape
         cfg = self.cfg
-        q, k, v = self.project_qkv(x, cos, sin)
+        if doc_start is not None and cfg.attn_impl == "sdpa":
+            raise NotImplementedError(
+                "document bounds need attn_impl='hip'; the sdpa path has no "
+                "document mask")
+        q, k, v = self.project_qkv(x, cos, sin, doc_start)
         if cfg.attn_impl == "sdpa" and x.is_cuda:
             rep = cfg.num_heads // cfg.num_kv_heads
             qt = q.transpose(1, 2)
@@ -129,7 +135,8 @@ class Attention(nn.Module):
             o = F.scaled_dot_product_attention(qt, kt, vt, is_causal=True)
             o = o.transpose(1, 2).contiguous()
         else:
-            o = ops.attention(q, k, v, causal=True)
+            o = ops.attention(q, k, v, causal=True, doc_start=doc_start,
+                              doc_end=doc_end)
         return ops.linear(o.reshape(B, S, cfg.num_heads * cfg.head_dim),
                           self.o_proj.weight)
 
@@ -164,10 +171,10 @@ class Block(nn.Module):
         self.post_attn_norm = RMSNorm(cfg.hidden_size, cfg.rms_eps)
         self.mlp = MLP(cfg)
 
-    def forward(self, x, res, cos, sin):
+    def forward(self, x, res, cos, sin, doc_start=None, doc_end=None):
         h, xr = ops.rmsnorm_residual(x, res, self.input_norm.weight,
                                      self.input_norm.eps)
-        a = self.attn(h, cos, sin)
+        a = self.attn(h, cos, sin, doc_start, doc_end)
         h2, xr2 = ops.rmsnorm_residual(a, xr, self.post_attn_norm.weight,
                                        self.post_attn_norm.eps)
         return self.mlp(h2), xr2
@@ -212,23 +219,39 @@ class LlamaModel(nn.Module):
             self._rope_cache = (S, cos, sin)
         return self._rope_cache[1], self._rope_cache[2]
 
-    def forward_hidden(self, input_ids: torch.Tensor) -> torch.Tensor:
+    def forward_hidden(self, input_ids: torch.Tensor,
+                       doc_start: torch.Tensor | None = None,
+                       doc_end: torch.Tensor | None = None) -> torch.Tensor:
         B, S = input_ids.shape
+        if doc_start is None and doc_end is not None:
+            raise ValueError("doc_end needs doc_start")
+        if doc_start is not None and self.cfg.attn_impl == "sdpa":
+            raise NotImplementedError(
+                "document bounds need attn_impl='hip'; the sdpa path has no "
+                "document mask")
+        if doc_start is not None and doc_end is None:
+            # once per forward, not once per layer
+            doc_end = ops.doc_end_from_start(doc_start)
         cos, sin = self._rope(S, input_ids.device)
         x = self.embed_tokens(input_ids)
         res = None  # pending residual, consumed by each fused norm
         for blk in self.layers:
             if self.activation_checkpointing and self.training:
                 x, res = torch.utils.checkpoint.checkpoint(
-                    blk, x, res, cos, sin, use_reentrant=False)
+                    blk, x, res, cos, sin, doc_start, doc_end,
+                    use_reentrant=False)
             else:
-                x, res = blk(x, res, cos, sin)
+                x, res = blk(x, res, cos, sin, doc_start, doc_end)
         y, _ = ops.rmsnorm_residual(x, res, self.norm.weight, self.norm.eps)
         return y
 
     def forward(self, input_ids: torch.Tensor,
-                labels: torch.Tensor | None = None):
-        x = self.forward_hidden(input_ids)
+                labels: torch.Tensor | None = None,
+                doc_start: torch.Tensor | None = None,
+                doc_end: torch.Tensor | None = None):
+        """doc_start / doc_end: packed-document bounds of input_ids
+        (ops.doc_bounds). Labels are not masked at document ends."""
+        x = self.forward_hidden(input_ids, doc_start, doc_end)
         logits = ops.linear(x, self.lm_head.weight)
         if labels is None:
             return logits

@@ -135,16 +135,24 @@ def rmsnorm_residual(x: torch.Tensor, res: torch.Tensor | None,
 # RoPE (Llama rotate-half convention)
 # --------------------------------------------------------------------------
 def rope_ref(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-             sign: float = 1.0) -> torch.Tensor:
-    """x: [B, S, H, D]; cos/sin: [>= S, D/2] fp32, row s = position s."""
+             sign: float = 1.0,
+             doc_start: torch.Tensor | None = None) -> torch.Tensor:
+    """x: [B, S, H, D]; cos/sin: [>= S, D/2] fp32, row s = position s, or
+    position s - doc_start[b, s] with packed-document bounds."""
     B, S, H, D = x.shape
     if cos.shape[0] < S or sin.shape[0] < S:
         raise ValueError(
             f"rope table has {cos.shape[0]} rows, sequence needs {S}")
     xf = x.float()
     x1, x2 = xf[..., : D // 2], xf[..., D // 2:]
-    cs = cos[:S].reshape(1, S, 1, D // 2)
-    sn = sin[:S].reshape(1, S, 1, D // 2) * sign
+    if doc_start is None:
+        cs = cos[:S].reshape(1, S, 1, D // 2)
+        sn = sin[:S].reshape(1, S, 1, D // 2) * sign
+    else:
+        pos = (torch.arange(S, device=x.device).unsqueeze(0)
+               - doc_start.long())
+        cs = cos[pos].reshape(B, S, 1, D // 2)
+        sn = sin[pos].reshape(B, S, 1, D // 2) * sign
     return torch.cat([x1 * cs - x2 * sn, x2 * cs + x1 * sn], dim=-1).to(x.dtype)
 
 
@@ -176,49 +184,74 @@ def apply_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.T
 # Packed-QKV split + RoPE (one pass over the fused qkv projection output)
 # --------------------------------------------------------------------------
 def qkv_rope_ref(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-                 Hq: int, Hkv: int, D: int, sign: float = 1.0):
+                 Hq: int, Hkv: int, D: int, sign: float = 1.0,
+                 doc_start: torch.Tensor | None = None):
     """fp32 reference. qkv: [B, S, (Hq+2Hkv)*D]; returns roped q, k and
     copied v with contiguous [B,S,H,D] layouts."""
     B, S, _ = qkv.shape
+    if doc_start is not None:
+        validate_doc_bounds(doc_start, None, B, S)
     parts = qkv.view(B, S, Hq + 2 * Hkv, D)
     q = parts[:, :, :Hq].contiguous()
     k = parts[:, :, Hq:Hq + Hkv].contiguous()
     v = parts[:, :, Hq + Hkv:].contiguous()
-    return (rope_ref(q, cos, sin, sign), rope_ref(k, cos, sin, sign), v)
+    return (rope_ref(q, cos, sin, sign, doc_start),
+            rope_ref(k, cos, sin, sign, doc_start), v)
 
 
 class _QKVRopeFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, cos, sin, Hq, Hkv, D):
-        ctx.save_for_backward(cos, sin)
+    def forward(ctx, qkv, cos, sin, Hq, Hkv, D, doc_start=None):
         ctx.dims = (Hq, Hkv, D)
+        ctx.docs = doc_start is not None
+        if ctx.docs:
+            ctx.save_for_backward(cos, sin, doc_start)
+        else:
+            ctx.save_for_backward(cos, sin)
         if qkv.is_cuda:
-            q, k, v = _require_ext("qkv_rope").qkv_rope_fwd(
-                qkv.contiguous(), cos, sin, Hq, Hkv, D)
+            ext = _require_ext("qkv_rope")
+            if ctx.docs:
+                q, k, v = ext.qkv_rope_fwd(qkv.contiguous(), cos, sin, Hq,
+                                           Hkv, D, doc_start)
+            else:
+                q, k, v = ext.qkv_rope_fwd(qkv.contiguous(), cos, sin, Hq,
+                                           Hkv, D)
             return q, k, v
-        return qkv_rope_ref(qkv, cos, sin, Hq, Hkv, D)
+        return qkv_rope_ref(qkv, cos, sin, Hq, Hkv, D, 1.0, doc_start)
 
     @staticmethod
     def backward(ctx, dq, dk, dv):
-        cos, sin = ctx.saved_tensors
+        saved = ctx.saved_tensors   # read once (activation checkpointing)
+        cos, sin = saved[:2]
+        ds = saved[2] if ctx.docs else None
         Hq, Hkv, D = ctx.dims
         if dq.is_cuda:
-            dqkv = _C.qkv_rope_bwd(dq.contiguous(), dk.contiguous(),
-                                   dv.contiguous(), cos, sin)
+            if ctx.docs:
+                dqkv = _C.qkv_rope_bwd(dq.contiguous(), dk.contiguous(),
+                                       dv.contiguous(), cos, sin, ds)
+            else:
+                dqkv = _C.qkv_rope_bwd(dq.contiguous(), dk.contiguous(),
+                                       dv.contiguous(), cos, sin)
         else:
             B, S = dq.shape[:2]
-            dqf = rope_ref(dq, cos, sin, -1.0).view(B, S, Hq * D)
-            dkf = rope_ref(dk, cos, sin, -1.0).view(B, S, Hkv * D)
+            dqf = rope_ref(dq, cos, sin, -1.0, ds).view(B, S, Hq * D)
+            dkf = rope_ref(dk, cos, sin, -1.0, ds).view(B, S, Hkv * D)
             dqkv = torch.cat([dqf, dkf, dv.reshape(B, S, Hkv * D)], dim=-1)
-        return dqkv, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None
 
 
 def qkv_rope(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-             Hq: int, Hkv: int, D: int):
+             Hq: int, Hkv: int, D: int,
+             doc_start: torch.Tensor | None = None):
     """Split the packed qkv projection [B,S,(Hq+2Hkv)*D] into contiguous
     q/k/v with RoPE applied to q and k — one kernel instead of three
-    splits + two rope launches (GEMM-packing lever, ROADMAP §1a)."""
-    return _QKVRopeFn.apply(qkv, cos, sin, Hq, Hkv, D)
+    splits + two rope launches (GEMM-packing lever, ROADMAP §1a). With
+    packed-document bounds (doc_bounds) a token's position is counted from
+    the first token of its document."""
+    if doc_start is None:
+        return _QKVRopeFn.apply(qkv, cos, sin, Hq, Hkv, D)
+    return _QKVRopeFn.apply(qkv, cos, sin, Hq, Hkv, D,
+                            _doc_tensor(doc_start, qkv, "doc_start"))
 
 
 # --------------------------------------------------------------------------
@@ -358,9 +391,82 @@ def grad_norm_finalize_(partials: torch.Tensor, out: torch.Tensor, *,
 # --------------------------------------------------------------------------
 # Flash attention (causal, GQA)
 # --------------------------------------------------------------------------
+def doc_bounds(input_ids: torch.Tensor, eos_token_id: int):
+    """Packed-document bounds of a [B, S] token batch, as int32 [B, S]:
+    doc_start[b, i] is the row index of the first token of the document
+    token i belongs to and doc_end[b, i] one past its last. The token after
+    an EOS starts a new document; the EOS belongs to the document it ends.
+    Plain tensor ops with no host sync and no data-dependent shape, so it
+    runs inside a captured step; once per micro-batch."""
+    B, S = input_ids.shape
+    idx = torch.arange(S, device=input_ids.device, dtype=torch.int32)
+    idx = idx.unsqueeze(0).expand(B, S)
+    eos = input_ids == eos_token_id
+    first = torch.ones_like(eos)
+    first[:, 1:] = eos[:, :-1]
+    start = torch.cummax(torch.where(first, idx, torch.zeros_like(idx)),
+                         dim=1).values
+    last = eos.clone()
+    last[:, -1] = True
+    ends = torch.where(last, idx + 1, torch.full_like(idx, S))
+    end = torch.cummin(ends.flip(1), dim=1).values.flip(1)
+    return start.contiguous(), end.contiguous()
+
+
+def doc_end_from_start(doc_start: torch.Tensor) -> torch.Tensor:
+    """doc_end for a valid doc_start: a document ends where the next one
+    starts, the last at S. No host sync."""
+    B, S = doc_start.shape
+    idx = torch.arange(S, device=doc_start.device, dtype=doc_start.dtype)
+    idx = idx.unsqueeze(0).expand(B, S)
+    first = doc_start == idx
+    # a start at i ends the document of token i-1 at i
+    ends = torch.full_like(doc_start, S)
+    ends[:, :-1] = torch.where(first[:, 1:], idx[:, 1:],
+                               torch.full_like(idx[:, 1:], S))
+    return torch.cummin(ends.flip(1), dim=1).values.flip(1).contiguous()
+
+
+def validate_doc_bounds(doc_start: torch.Tensor,
+                        doc_end: torch.Tensor | None, B: int, S: int) -> None:
+    """Host-side check of the bounds contract (CPU path only; the GPU
+    kernels never read the tensors on the host and clamp instead)."""
+    for name, t in (("doc_start", doc_start), ("doc_end", doc_end)):
+        if t is None:
+            continue
+        if t.dtype != torch.int32 or tuple(t.shape) != (B, S):
+            raise ValueError(
+                f"{name} must be int32 [{B}, {S}], got {t.dtype} "
+                f"{tuple(t.shape)}")
+    idx = torch.arange(S, device=doc_start.device).unsqueeze(0)
+    ds = doc_start.long()
+    if bool((ds < 0).any()) or bool((ds > idx).any()):
+        raise ValueError("doc_start must satisfy 0 <= doc_start[b, i] <= i")
+    if bool((ds[:, 1:] < ds[:, :-1]).any()):
+        raise ValueError("doc_start must be non-decreasing along a row")
+    if bool((torch.gather(ds, 1, ds) != ds).any()):
+        raise ValueError("doc_start must be constant inside a document")
+    if doc_end is not None:
+        want = doc_end_from_start(doc_start)
+        if not torch.equal(doc_end, want):
+            raise ValueError("doc_end does not match doc_start")
+
+
+def _doc_tensor(t: torch.Tensor, like: torch.Tensor, name: str):
+    B, S = like.shape[:2]
+    if t.dtype != torch.int32 or tuple(t.shape) != (B, S):
+        raise ValueError(
+            f"{name} must be int32 [{B}, {S}], got {t.dtype} {tuple(t.shape)}")
+    if t.device != like.device:
+        raise ValueError(f"{name} must be on {like.device}, is on {t.device}")
+    return t.contiguous()
+
+
 def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                  causal: bool = True) -> torch.Tensor:
-    """fp32 reference attention. q: [B,S,Hq,D], k/v: [B,S,Hkv,D]."""
+                  causal: bool = True,
+                  doc_start: torch.Tensor | None = None) -> torch.Tensor:
+    """fp32 reference attention. q: [B,S,Hq,D], k/v: [B,S,Hkv,D]. With
+    doc_start (int32 [B,S]) query i sees keys doc_start[b, i] .. i."""
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
     rep = Hq // Hkv
@@ -371,6 +477,10 @@ def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     if causal:
         mask = torch.triu(torch.ones(S, S, dtype=torch.bool, device=q.device), 1)
         s = s.masked_fill(mask, float("-inf"))
+    if doc_start is not None:
+        keys = torch.arange(S, device=q.device).view(1, 1, 1, S)
+        before = keys < doc_start.long().view(B, 1, S, 1)
+        s = s.masked_fill(before, float("-inf"))
     p = torch.softmax(s, dim=-1)
     o = torch.matmul(p, vf)
     return o.permute(0, 2, 1, 3).to(q.dtype)
@@ -378,34 +488,68 @@ def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal):
+    def forward(ctx, q, k, v, causal, doc_start=None, doc_end=None):
         if q.is_cuda:
             ext = _require_ext("flash_attention")
             if not hasattr(ext, "attn_fwd"):
                 raise RuntimeError(
                     "HIP flash attention kernel missing from extension; "
                     "rebuild the extension")
-            o, lse = ext.attn_fwd(q, k, v, causal)
-            ctx.save_for_backward(q, k, v, o, lse)
             ctx.causal = causal
+            ctx.docs = doc_start is not None
+            if ctx.docs:
+                o, lse = ext.attn_fwd(q, k, v, causal, 0, doc_start)
+                ctx.save_for_backward(q, k, v, o, lse, doc_start, doc_end)
+            else:
+                o, lse = ext.attn_fwd(q, k, v, causal)
+                ctx.save_for_backward(q, k, v, o, lse)
             return o
         # CPU path: differentiable reference (no custom backward needed).
         raise RuntimeError("use attention() entry point for CPU tensors")
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
-        dq, dk, dv = _C.attn_bwd(q, k, v, o, lse, do.contiguous(), ctx.causal)
-        return dq, dk, dv, None
+        saved = ctx.saved_tensors   # read once (activation checkpointing)
+        q, k, v, o, lse = saved[:5]
+        if ctx.docs:
+            ds, de = saved[5:]
+            dq, dk, dv = _C.attn_bwd(q, k, v, o, lse, do.contiguous(),
+                                     ctx.causal, False, 1, ds, de)
+        else:
+            dq, dk, dv = _C.attn_bwd(q, k, v, o, lse, do.contiguous(),
+                                     ctx.causal)
+        return dq, dk, dv, None, None, None
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-              causal: bool = True) -> torch.Tensor:
-    """Causal GQA attention: HIP flash kernel on GPU, reference on CPU."""
+              causal: bool = True, doc_start: torch.Tensor | None = None,
+              doc_end: torch.Tensor | None = None) -> torch.Tensor:
+    """Causal GQA attention: HIP flash kernel on GPU, reference on CPU.
+
+    doc_start / doc_end (int32 [B,S], see doc_bounds) restrict query i to
+    the keys of its own packed document, doc_start[b, i] .. i; doc_end is
+    derived when omitted. The GPU kernels clamp what they read from the
+    tensors, so malformed bounds give wrong numbers, never a bad access;
+    the CPU path validates them and raises ValueError."""
+    if doc_start is None:
+        if doc_end is not None:
+            raise ValueError("doc_end needs doc_start")
+        if q.is_cuda:
+            return _FlashAttnFn.apply(q.contiguous(), k.contiguous(),
+                                      v.contiguous(), causal)
+        return attention_ref(q, k, v, causal)
+    if not causal:
+        raise ValueError("document bounds need causal=True")
+    doc_start = _doc_tensor(doc_start, q, "doc_start")
+    if doc_end is not None:
+        doc_end = _doc_tensor(doc_end, q, "doc_end")
     if q.is_cuda:
+        if doc_end is None:
+            doc_end = doc_end_from_start(doc_start)
         return _FlashAttnFn.apply(q.contiguous(), k.contiguous(),
-                                  v.contiguous(), causal)
-    return attention_ref(q, k, v, causal)
+                                  v.contiguous(), causal, doc_start, doc_end)
+    validate_doc_bounds(doc_start, doc_end, q.shape[0], q.shape[1])
+    return attention_ref(q, k, v, causal, doc_start)
 
 
 # --------------------------------------------------------------------------
@@ -1005,7 +1149,8 @@ __all__ = [
     "dgrad", "dgrad_impl", "dgrad_transposed", "transpose_2d_",
     "rmsnorm", "rmsnorm_ref", "apply_rope", "rope_ref", "fused_adamw_",
     "attention", "attention_ref", "cross_entropy", "layernorm",
-    "qkv_rope", "qkv_rope_ref", "swiglu", "swiglu_ref",
+    "qkv_rope", "qkv_rope_ref", "doc_bounds", "doc_end_from_start",
+    "validate_doc_bounds", "swiglu", "swiglu_ref",
     "hip_ext_available",
     "grad_sumsq_blocks", "grad_sumsq_", "grad_norm_finalize_",
     "attention_decode_ragged", "qkv_rope_append_",

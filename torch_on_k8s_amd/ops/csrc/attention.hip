@@ -32,6 +32,11 @@
 //    All kernels: 0 scratch spill.
 //  * fwd v4, fused dK+dV and dQ take their block from xcd_block_index():
 //    the blocks that share a kv head's tiles run on one XCD's L2.
+//  * Packed documents (template flag DOC on fwd v4, fused dK+dV and the
+//    8-wave dQ): optional int32 [B,S] doc_start / doc_end bounds add a
+//    second cut next to the causal one - query i sees keys doc_start[i]..i.
+//    Key tiles of earlier documents are never staged. See DocRows and the
+//    fused kernel; measurements in profiles/attn_docs.log.
 //
 // Measured (B=2 S=4096 Hq=32 Hkv=8 D=128 causal, random data): fwd v3
 // 358-371 TF (parity with torch's aotriton flash), v4 see
@@ -462,12 +467,55 @@ __global__ __launch_bounds__(NTHREADS) void attn_fwd_kernel_v3(
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
-template <int D, bool CAUSAL>
+// Document bounds of a wave's 32 q rows (packed-document training): query i
+// sees key j iff doc_start[b, i] <= j <= i. The forward and dQ kernels own
+// one q row per lane, so the bound is one register next to q_reg.
+//  * dstart: this lane's bound, clamped into [0, row]. Rows past S take
+//    row S-1's, so the wave's last lane still holds the largest bound.
+//  * wave_min / wave_max: the bounds of the wave's first and last row
+//    (doc_start is non-decreasing), wave-uniform. A tile that ends at or
+//    before wave_min is dead for the whole wave; a tile that begins before
+//    wave_max needs the per-element mask.
+//  * n_begin: first key tile of the block, the tile of row m0's bound,
+//    clamped into [0, tile of m0].
+// Nothing here is trusted: every value derived from the tensor is clamped
+// into the range the plain causal kernel touches, so a malformed tensor
+// gives wrong numbers and no out-of-range access.
+//
+// The kernels take the [B, S] tensor as a trailing parameter pack: one
+// `const int*` with DOC, empty without, so the plain instantiations keep
+// their argument list. Their DocRows is the specialisation below whose
+// members are compile-time zeros: with run-time zeros the D = 64 kernels
+// came out four VGPRs larger, though every use folds away in the end.
+DEVINL const int* first_arg(const int* p) { return p; }
+
+template <bool DOC>
+struct DocRows {
+  int dstart, wave_min, wave_max, n_begin;
+  DEVINL DocRows(int b, int S, int m0, int qrow, const int* doc_start) {
+    const int* dsp = doc_start + (long)b * S;
+    const int row = min(qrow, S - 1);
+    dstart = max(0, min(dsp[row], row));
+    wave_min = __builtin_amdgcn_readfirstlane(dstart);
+    wave_max = __builtin_amdgcn_readlane(dstart, 31);
+    n_begin = max(0, min(dsp[m0], m0)) / BN * BN;
+  }
+};
+
+template <>
+struct DocRows<false> {
+  static constexpr int dstart = 0, wave_min = 0, wave_max = 0, n_begin = 0;
+  DEVINL DocRows(int, int, int, int) {}
+};
+
+template <int D, bool CAUSAL, bool DOC = false, typename... DOCARG>
 __global__ __launch_bounds__(NTHREADS) void attn_fwd_kernel_v4(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ vt, bf16_t* __restrict__ o,
     float* __restrict__ lse, int B, int S, int Hq, int Hkv, int S_pad,
-    float scale) {
+    float scale, DOCARG... doc_start) {
+  static_assert(!DOC || CAUSAL, "document bounds refine the causal mask");
+  static_assert(sizeof...(DOCARG) == (DOC ? 1 : 0), "one tensor with DOC");
   constexpr int QC = D / 16;    // Q B-fragments (k-slots of 16)
   constexpr int DT = D / 32;    // O col tiles of 32
   constexpr int BM3 = NW * 32;  // 256 q rows per block
@@ -510,18 +558,19 @@ __global__ __launch_bounds__(NTHREADS) void attn_fwd_kernel_v4(
   // m_run: running row max of score*scale*log2e (log2 units)
   float m_run = NEG_INF, l_run = 0.f;
   const float c2 = scale * LOG2E;
+  const DocRows<DOC> doc(b, S, m0, qrow, doc_start...);
 
   TileStage<D> k_st;
   TileStageT<D> v_st;
   const int n_end = CAUSAL ? min(S, m0 + BM3) : S;
-  k_st.issue(kp, 0, S, kv_tok);
-  v_st.issue(vtp, 0, S_pad);
+  k_st.issue(kp, doc.n_begin, S, kv_tok);
+  v_st.issue(vtp, doc.n_begin, S_pad);
   k_st.write_rm(smem);
   v_st.write(smem + KB);
   __syncthreads();
   int cur = 0;
 
-  for (int n0 = 0; n0 < n_end; n0 += BN) {
+  for (int n0 = doc.n_begin; n0 < n_end; n0 += BN) {
     char* k_lds = smem + cur * (2 * KB);
     char* vt_lds = k_lds + KB;
     const bool more = n0 + BN < n_end;
@@ -530,7 +579,8 @@ __global__ __launch_bounds__(NTHREADS) void attn_fwd_kernel_v4(
       v_st.issue(vtp, n0 + BN, S_pad);
     }
 
-    const bool strip_live = !CAUSAL || (n0 <= m0w + 31);
+    const bool strip_live = (!CAUSAL || (n0 <= m0w + 31)) &&
+                            (!DOC || n0 + BN > doc.wave_min);
     if (strip_live) {
       // S^T strips (two 32-kv subtiles x 32 q cols), raw (unscaled)
       f32x16 st[2];
@@ -563,16 +613,21 @@ __global__ __launch_bounds__(NTHREADS) void attn_fwd_kernel_v4(
       __builtin_amdgcn_sched_group_barrier(0x008, QC, 0);
       __builtin_amdgcn_s_setprio(0);
 
-      // mask (edge tiles only) + in-lane row max of the raw scores
+      // mask (edge tiles only) + in-lane row max of the raw scores. With
+      // document bounds a row can meet whole tiles of -inf before its
+      // first live key; m_run stays -inf through them and the two guards
+      // below (alpha = 0, neg_m = 0) keep p, l_run and O at exactly 0.
       const bool needs_mask = (n0 + BN > S) ||
-                              (CAUSAL && (n0 + BN - 1 > m0w));
+                              (CAUSAL && (n0 + BN - 1 > m0w)) ||
+                              (DOC && n0 < doc.wave_max);
       if (needs_mask) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int kvg = n0 + ks * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if ((CAUSAL && kvg > qrow) || kvg >= S || qrow >= S)
+            if ((CAUSAL && kvg > qrow) || kvg >= S || qrow >= S ||
+                (DOC && kvg < doc.dstart))
               st[ks][r] = NEG_INF;
           }
       }
@@ -1275,12 +1330,23 @@ DEVINL void dkdv_tile_sdp(const char* st, const char* v_lds,
 }
 
 // Part 2: P = exp2(c2*S'), dS = P*dP', dV += P^T·dO, dK += dS^T·Q.
-template <int D, bool CAUSAL, int NH>
+// Document bounds (DOC): a lane owns one key, so its bound is doc_end of
+// that key, one value per 32-key half: q row qg sees the key iff
+// kvrow <= qg < dend, which is one unsigned compare, qg - kvrow < dlen,
+// with dlen = dend - kvrow (0 for a key past S): as many operations per
+// element as the plain chain. The chain is a select under a uniform flag,
+// not a branch, so it runs on every tile; with separate compares for the
+// causal cut and the bound the whole backward was 6 % slower at one
+// document per row (profiles/attn_docs.log). dend_min is the half's
+// smallest doc_end (its first key's); the per-element mask is also needed
+// once the tile's last real q row reaches it.
+template <int D, bool CAUSAL, int NH, bool DOC>
 DEVINL void dkdv_tile_acc(const char* st, const f32x16 (&sv)[2],
                           const f32x16 (&dpv)[2],
                           f32x16 (&dk_acc)[2][D / 32],
                           f32x16 (&dv_acc)[2][D / 32], int m0, int n0w,
-                          int S, int lane, int hi, float c2) {
+                          int S, int lane, int hi, float c2,
+                          const int (&dlen)[2], const int (&dend_min)[2]) {
   constexpr int DT = D / 32;
   constexpr int TB = DkdvStage<D>::TB;
   const char* qt_lds = st + 2 * TB;
@@ -1293,14 +1359,17 @@ DEVINL void dkdv_tile_acc(const char* st, const f32x16 (&sv)[2],
     const int kvrow = ks0 + (lane & 31);
     // q-side padding is already in the row constant; only the diagonal
     // and the key tail need the per-element mask (uniform flag)
-    const bool need_mask = (CAUSAL && m0 < ks0 + 32) || (ks0 + 32 > S);
+    const bool need_mask = (CAUSAL && m0 < ks0 + 32) || (ks0 + 32 > S) ||
+                           (DOC && min(m0 + QROWS, S) > dend_min[hh]);
     f32x16 pt, dst;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       float pv = __builtin_amdgcn_exp2f(sv[hh][r] * c2);
       if (need_mask) {
         const int qg = m0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        if (!(kvrow < S && (!CAUSAL || qg >= kvrow))) pv = 0.f;
+        if (DOC ? !((unsigned)(qg - kvrow) < (unsigned)dlen[hh])
+                : !(kvrow < S && (!CAUSAL || qg >= kvrow)))
+          pv = 0.f;
       }
       pt[r] = pv;
       dst[r] = pv * dpv[hh][r];
@@ -1334,14 +1403,16 @@ DEVINL void dkdv_tile_acc(const char* st, const f32x16 (&sv)[2],
   }
 }
 
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, bool DOC = false, typename... DOCARG>
 __global__ __launch_bounds__(NTH_KV) void attn_bwd_dkdv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
     const bf16_t* __restrict__ q_t, const bf16_t* __restrict__ dot_t,
     const float* __restrict__ rc, bf16_t* __restrict__ dk,
     bf16_t* __restrict__ dv, int B, int S, int Hq, int Hkv, int S_pad,
-    float scale) {
+    float scale, DOCARG... doc_end) {
+  static_assert(sizeof...(DOCARG) == (DOC ? 1 : 0), "one tensor with DOC");
+  static_assert(!DOC || CAUSAL, "document bounds refine the causal mask");
   constexpr int QC = D / 16;
   constexpr int DT = D / 32;
   constexpr int BNK = NW_KV * 64;   // 256 keys per block
@@ -1398,6 +1469,29 @@ __global__ __launch_bounds__(NTH_KV) void attn_bwd_dkdv_kernel(
       }
 
   const int m_start = CAUSAL ? n0 : 0;   // n0 is a multiple of QROWS
+  // Document bounds: doc_end of the lane's key per half, clamped into
+  // (key, S] (keys past S take row S-1's and are masked as keys anyway);
+  // each half's smallest and largest value (first / last lane, doc_end is
+  // non-decreasing) made wave-uniform; and the end of the block's q loop,
+  // doc_end of the block's last key clamped into (n0, S]. No q row at or
+  // past m_end can see a key of this block. What stays in a register per
+  // half is dlen = doc_end - key (see dkdv_tile_acc). Without DOC the
+  // bounds are all S and dlen is unused.
+  int dlen[2] = {0, 0}, dend_min[2] = {S, S}, dend_max[2] = {S, S};
+  int m_end = S;
+  if constexpr (DOC) {
+    const int* dep = first_arg(doc_end...) + (long)b * S;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      const int key = n0w + hh * 32 + (lane & 31);
+      const int kvrow = min(key, S - 1);
+      const int dend = min(S, max(dep[kvrow], kvrow + 1));
+      dlen[hh] = key < S ? dend - key : 0;
+      dend_min[hh] = __builtin_amdgcn_readfirstlane(dend);
+      dend_max[hh] = __builtin_amdgcn_readlane(dend, 31);
+    }
+    m_end = min(S, max(dep[min(n0 + BNK, S) - 1], n0 + 1));
+  }
   const float c2 = LOG2E * scale;
   const long plane = (long)D * S_pad;
   const long head0 = (long)b * Hq + hkv * rep;
@@ -1413,21 +1507,26 @@ __global__ __launch_bounds__(NTH_KV) void attn_bwd_dkdv_kernel(
   int cur = 0;
 
   for (int g = 0; g < rep; ++g) {
-    for (int m0 = m_start; m0 < S; m0 += QROWS) {
+    for (int m0 = m_start; m0 < m_end; m0 += QROWS) {
       const char* st = smem + cur * STB;
       char* nst = smem + (cur ^ 1) * STB;
       // next tile: next q rows of this head, else the next head's first
       int gn = g, mn = m0 + QROWS;
-      if (mn >= S) {
+      if (mn >= m_end) {
         gn = g + 1;
         mn = m_start;
       }
       const bool more = gn < rep;
       // wave-uniform skip of key halves with no keys or entirely above
-      // the diagonal for this q tile; half 1 live implies half 0 live
-      const bool live0 = n0w < S && (!CAUSAL || m0 + QROWS > n0w);
-      const bool live1 =
-          n0w + 32 < S && (!CAUSAL || m0 + QROWS > n0w + 32);
+      // the diagonal for this q tile; half 1 live implies half 0 live.
+      // With document bounds a half is also dead once the q tile starts
+      // past the document of its last key; half 1 can then be live with
+      // half 0's keys all masked, which the two-half path handles.
+      const bool live0 = n0w < S && (!CAUSAL || m0 + QROWS > n0w) &&
+                         (!DOC || m0 < dend_max[0]);
+      const bool live1 = n0w + 32 < S &&
+                         (!CAUSAL || m0 + QROWS > n0w + 32) &&
+                         (!DOC || m0 < dend_max[1]);
 
       // the other buffer was last read before the previous barrier
       if (more)
@@ -1437,12 +1536,14 @@ __global__ __launch_bounds__(NTH_KV) void attn_bwd_dkdv_kernel(
       f32x16 sv[2], dpv[2];
       if (live1) {
         dkdv_tile_sdp<D, 2>(st, v_lds, k_reg, sv, dpv, wid * 64, lane, hi);
-        dkdv_tile_acc<D, CAUSAL, 2>(st, sv, dpv, dk_acc, dv_acc, m0, n0w, S,
-                                    lane, hi, c2);
+        dkdv_tile_acc<D, CAUSAL, 2, DOC>(st, sv, dpv, dk_acc, dv_acc, m0,
+                                         n0w, S, lane, hi, c2, dlen,
+                                         dend_min);
       } else if (live0) {
         dkdv_tile_sdp<D, 1>(st, v_lds, k_reg, sv, dpv, wid * 64, lane, hi);
-        dkdv_tile_acc<D, CAUSAL, 1>(st, sv, dpv, dk_acc, dv_acc, m0, n0w, S,
-                                    lane, hi, c2);
+        dkdv_tile_acc<D, CAUSAL, 1, DOC>(st, sv, dpv, dk_acc, dv_acc, m0,
+                                         n0w, S, lane, hi, c2, dlen,
+                                         dend_min);
       }
       if (more) stg.finish();
       __syncthreads();
@@ -1471,13 +1572,16 @@ __global__ __launch_bounds__(NTH_KV) void attn_bwd_dkdv_kernel(
 // Backward dQ v3: grid (ceil(S/256), Hq, B); 8 waves, wave = 32 q rows.
 // Q/dO in registers (lane owns q row); lse/Dsum are per-lane scalars.
 // ========================================================================
-template <int D, bool CAUSAL, bool XCD>
+template <int D, bool CAUSAL, bool XCD, bool DOC = false,
+          typename... DOCARG>
 __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
     const bf16_t* __restrict__ k_t, const float* __restrict__ lse,
     const float* __restrict__ dsum, bf16_t* __restrict__ dq, int B, int S,
-    int Hq, int Hkv, int S_pad, float scale) {
+    int Hq, int Hkv, int S_pad, float scale, DOCARG... doc_start) {
+  static_assert(sizeof...(DOCARG) == (DOC ? 1 : 0), "one tensor with DOC");
+  static_assert(!DOC || CAUSAL, "document bounds refine the causal mask");
   constexpr int QC = D / 16;
   constexpr int DT = D / 32;
   constexpr int BM3 = NW * 32;
@@ -1532,19 +1636,30 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) dq_acc[t][r] = 0.f;
 
+  const DocRows<DOC> doc(b, S, m0, qrow, doc_start...);
+  // With bounds the whole mask chain of a row is one unsigned compare:
+  // dstart <= kvg <= qrow, i.e. kvg - dstart < doc_len, with doc_len = 0
+  // for a row past S or without an lse (kvg <= qrow < S covers kvg < S).
+  // It holds two registers across the key loop where the plain chain holds
+  // qrow and lse_lane; a third (the bound next to those two) spilled this
+  // kernel at D = 128.
+  int doc_len = 0;
+  if (DOC)
+    doc_len = (qrow < S && lse_lane != NEG_INF) ? qrow - doc.dstart + 1 : 0;
+
   TileStage<D> k_st, v_st;
   TileStageT<D> kt_st;
   const int n_end = CAUSAL ? min(S, m0 + BM3) : S;
-  k_st.issue(kp, 0, S, kv_tok);
-  v_st.issue(vp, 0, S, kv_tok);
-  kt_st.issue(ktp, 0, S_pad);
+  k_st.issue(kp, doc.n_begin, S, kv_tok);
+  v_st.issue(vp, doc.n_begin, S, kv_tok);
+  kt_st.issue(ktp, doc.n_begin, S_pad);
   k_st.write_rm(smem);
   kt_st.write(smem + KB);
   v_st.write_rm(smem + 2 * KB);
   __syncthreads();
   int cur = 0;
 
-  for (int n0 = 0; n0 < n_end; n0 += BN) {
+  for (int n0 = doc.n_begin; n0 < n_end; n0 += BN) {
     char* k_lds = smem + cur * (3 * KB);
     char* kt_lds = k_lds + KB;
     char* v_lds = k_lds + 2 * KB;
@@ -1555,7 +1670,8 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
       kt_st.issue(ktp, n0 + BN, S_pad);
     }
 
-    const bool strip_live = !CAUSAL || (n0 <= m0w + 31);
+    const bool strip_live = (!CAUSAL || (n0 <= m0w + 31)) &&
+                            (!DOC || n0 + BN > doc.wave_min);
     if (strip_live) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {   // two 32-kv subtiles
@@ -1582,15 +1698,21 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_dq_kernel(
         // causal-valid and in-bounds -> the per-element mask chain is
         // dead VALU work (PMC r2: bwd is ~11 VALU/MFMA). One loop with
         // a uniform flag keeps the register footprint shared.
+        // Document bounds: a subtile that begins before the wave's largest
+        // bound holds keys of an earlier document for some row. Their
+        // exp2(s - lse) can be anything up to +inf (lse belongs to another
+        // document); it is replaced by 0 before it meets a product.
         const bool need_mask = (CAUSAL && n0 + ks * 32 + 32 > m0w) ||
-                               (n0 + ks * 32 + 32 > S) || (m0w + 32 > S);
+                               (n0 + ks * 32 + 32 > S) || (m0w + 32 > S) ||
+                               (DOC && n0 + ks * 32 < doc.wave_max);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sv[r], c2, nl2));
           if (need_mask) {
             const int kvg = n0 + ks * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (!(qrow < S && kvg < S && (!CAUSAL || kvg <= qrow) &&
-                  lse_lane != NEG_INF))
+            if (DOC ? !((unsigned)(kvg - doc.dstart) < (unsigned)doc_len)
+                    : !(qrow < S && kvg < S && (!CAUSAL || kvg <= qrow) &&
+                        lse_lane != NEG_INF))
               pv = 0.f;
           }
           dst[r] = pv * (dpv[r] - ds_lane);
@@ -2002,10 +2124,26 @@ extern "C" {
 hipError_t tok_attn_fwd(const void* q, const void* k, const void* vt, void* o,
                         float* lse, int B, int S, int Hq, int Hkv, int D,
                         int S_pad, int causal, hipStream_t stream,
-                        int variant) {
+                        int variant, const int* doc_start) {
   dim3 grid((S + NW * 32 - 1) / (NW * 32), Hq, B);
   const float scale = 1.f / sqrtf((float)D);
   if (variant != 0 && variant != 1) return hipErrorInvalidValue;
+  // doc_start: optional int32 [B, S] document bounds (DocRows); only the
+  // causal v4 kernel has the instantiation
+  if (doc_start) {
+    if (!causal || variant != 0) return hipErrorInvalidValue;
+    if (D == 128)
+      attn_fwd_kernel_v4<128, true, true><<<grid, NTHREADS, 0, stream>>>(
+          (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)o,
+          lse, B, S, Hq, Hkv, S_pad, scale, doc_start);
+    else if (D == 64)
+      attn_fwd_kernel_v4<64, true, true><<<grid, NTHREADS, 0, stream>>>(
+          (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)o,
+          lse, B, S, Hq, Hkv, S_pad, scale, doc_start);
+    else
+      return hipErrorInvalidValue;
+    return hipGetLastError();
+  }
 #define LAUNCH_FWD(DD, CC)                                                    \
   do {                                                                        \
     if (variant == 1)                                                         \
@@ -2015,7 +2153,7 @@ hipError_t tok_attn_fwd(const void* q, const void* k, const void* vt, void* o,
     else                                                                      \
       attn_fwd_kernel_v4<DD, CC><<<grid, NTHREADS, 0, stream>>>(              \
           (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)o, \
-          lse, B, S, Hq, Hkv, S_pad, scale);                                  \
+          lse, B, S, Hq, Hkv, S_pad, scale);                         \
   } while (0)
   if (D == 128) { if (causal) LAUNCH_FWD(128, true); else LAUNCH_FWD(128, false); }
   else if (D == 64) { if (causal) LAUNCH_FWD(64, true); else LAUNCH_FWD(64, false); }
@@ -2038,9 +2176,17 @@ hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
                         float* dsum_ws, float* rc_ws, void* dq, void* dk,
                         void* dv, int B, int S, int Hq, int Hkv, int D,
                         int S_pad, int causal, hipStream_t stream, int split,
-                        int dq_variant) {
+                        int dq_variant, const int* doc_start,
+                        const int* doc_end) {
   const float scale = 1.f / sqrtf((float)D);
   if (dq_variant < 0 || dq_variant > 2) return hipErrorInvalidValue;
+  // doc_start / doc_end: optional int32 [B, S] document bounds, both or
+  // neither; only the causal default pair (fused dK+dV, dq_variant 1) has
+  // the instantiations
+  const bool docs = doc_start != nullptr;
+  if (docs != (doc_end != nullptr)) return hipErrorInvalidValue;
+  if (docs && (!causal || split || dq_variant != 1))
+    return hipErrorInvalidValue;
   dim3 gpre((S + PRE_ROWS - 1) / PRE_ROWS, Hq, B);
   if (D == 128)
     attn_bwd_pre_kernel<128><<<gpre, 256, 0, stream>>>(
@@ -2056,6 +2202,24 @@ hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
   dim3 gkv((S + NW * 32 - 1) / (NW * 32), Hkv, B);
   dim3 gkvf((S + NW_KV * 64 - 1) / (NW_KV * 64), Hkv, B);
   dim3 gq((S + NW * 32 - 1) / (NW * 32), Hq, B);
+#define LAUNCH_BWD_DOC(DD)                                                    \
+  do {                                                                        \
+    attn_bwd_dkdv_kernel<DD, true, true><<<gkvf, NTH_KV, 0, stream>>>(        \
+        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,                 \
+        (const bf16_t*)dout, (const bf16_t*)q_t, (const bf16_t*)dot_t,        \
+        rc_ws, (bf16_t*)dk, (bf16_t*)dv, B, S, Hq, Hkv, S_pad, scale,         \
+        doc_end);                                                             \
+    attn_bwd_dq_kernel<DD, true, true, true><<<gq, NTHREADS, 0, stream>>>(    \
+        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,                 \
+        (const bf16_t*)dout, (const bf16_t*)k_t, lse, dsum_ws,                \
+        (bf16_t*)dq, B, S, Hq, Hkv, S_pad, scale,                            \
+        doc_start);                                                           \
+  } while (0)
+  if (docs) {
+    if (D == 128) LAUNCH_BWD_DOC(128); else LAUNCH_BWD_DOC(64);
+    return hipGetLastError();
+  }
+#undef LAUNCH_BWD_DOC
 #define LAUNCH_BWD(DD, CC)                                                    \
   do {                                                                        \
     if (split) {                                                              \
@@ -2083,12 +2247,12 @@ hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
       attn_bwd_dq_kernel<DD, CC, true><<<gq, NTHREADS, 0, stream>>>(          \
           (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,               \
           (const bf16_t*)dout, (const bf16_t*)k_t, lse, dsum_ws,              \
-          (bf16_t*)dq, B, S, Hq, Hkv, S_pad, scale);                          \
+          (bf16_t*)dq, B, S, Hq, Hkv, S_pad, scale);                 \
     else                                                                      \
       attn_bwd_dq_kernel<DD, CC, false><<<gq, NTHREADS, 0, stream>>>(         \
           (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,               \
           (const bf16_t*)dout, (const bf16_t*)k_t, lse, dsum_ws,              \
-          (bf16_t*)dq, B, S, Hq, Hkv, S_pad, scale);                          \
+          (bf16_t*)dq, B, S, Hq, Hkv, S_pad, scale);                 \
   } while (0)
   if (D == 128) { if (causal) LAUNCH_BWD(128, true); else LAUNCH_BWD(128, false); }
   else { if (causal) LAUNCH_BWD(64, true); else LAUNCH_BWD(64, false); }

@@ -32,12 +32,13 @@ hipError_t tok_swiglu_bwd(const void* dout, const void* gu, void* dgu,
 hipError_t tok_qkv_rope_fwd(const void* qkv, void* q, void* k, void* v,
                             const float* cos_tab, const float* sin_tab,
                             long tokens, int Hq, int Hkv, int D,
-                            long S, hipStream_t stream);
+                            long S, hipStream_t stream,
+                            const int* doc_start);
 hipError_t tok_qkv_rope_bwd(const void* dq, const void* dk, const void* dv,
                             void* dqkv, const float* cos_tab,
                             const float* sin_tab, long tokens, int Hq,
                             int Hkv, int D, long S,
-                            hipStream_t stream);
+                            hipStream_t stream, const int* doc_start);
 hipError_t tok_rope(const void* x, void* y, const float* cos_tab,
                     const float* sin_tab, long rows_total, int heads, int D,
                     long S, float sign, hipStream_t stream);
@@ -66,14 +67,15 @@ hipError_t tok_mfma_probe_32x32x16(const void* A, const void* B, float* D,
 hipError_t tok_attn_fwd(const void* q, const void* k, const void* vt, void* o,
                         float* lse, int B, int S, int Hq, int Hkv, int D,
                         int S_pad, int causal, hipStream_t stream,
-                        int variant);
+                        int variant, const int* doc_start);
 hipError_t tok_attn_bwd(const void* q, const void* k, const void* v,
                         const void* o, const void* dout, const void* q_t,
                         const void* k_t, const void* dot_t, const float* lse,
                         float* dsum_ws, float* rc_ws, void* dq, void* dk,
                         void* dv, int B, int S, int Hq, int Hkv, int D,
                         int S_pad, int causal, hipStream_t stream, int split,
-                        int dq_variant);
+                        int dq_variant, const int* doc_start,
+                        const int* doc_end);
 hipError_t tok_transpose_head(const void* in, void* out, int B, int S, int H,
                               int D, int S_pad, hipStream_t stream);
 hipError_t tok_transpose_2d(const void* in, void* out, long R, long C,
@@ -251,10 +253,28 @@ at::Tensor swiglu_bwd(at::Tensor dout, at::Tensor gu) {
   return dgu;
 }
 
+// Optional packed-document bounds: int32 [B, S], contiguous, on the data's
+// device. Returns nullptr when absent. The values are never read on the
+// host; the kernels clamp them.
+static const int* doc_bounds_ptr(const c10::optional<at::Tensor>& t,
+                                 const at::Tensor& like, long B, long S,
+                                 const char* name) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->device() == like.device(), name,
+              " must be on the same device as the data");
+  TORCH_CHECK(t->scalar_type() == at::kInt, name, " must be int32");
+  TORCH_CHECK(t->is_contiguous() && t->dim() == 2 && t->size(0) == B &&
+                  t->size(1) == S,
+              name, " must be a contiguous [B, S] tensor");
+  return t->data_ptr<int>();
+}
+
 // qkv: [B, S, (Hq+2Hkv)*D] -> roped q [B,S,Hq,D], k [B,S,Hkv,D], v [B,S,Hkv,D]
+// doc_start: positions count from each token's document start when given
 std::vector<at::Tensor> qkv_rope_fwd(at::Tensor qkv, at::Tensor cos_tab,
                                      at::Tensor sin_tab, long Hq, long Hkv,
-                                     long D) {
+                                     long D,
+                                     c10::optional<at::Tensor> doc_start) {
   CHECK_BF16_CUDA(qkv);
   TORCH_CHECK(cos_tab.scalar_type() == at::kFloat && cos_tab.is_contiguous());
   TORCH_CHECK(sin_tab.scalar_type() == at::kFloat && sin_tab.is_contiguous());
@@ -266,18 +286,20 @@ std::vector<at::Tensor> qkv_rope_fwd(at::Tensor qkv, at::Tensor cos_tab,
   TORCH_CHECK(sin_tab.numel() == cos_tab.numel(), "cos/sin shape mismatch");
   TORCH_CHECK(table_rows >= S, "rope table has ", table_rows,
               " rows, sequence needs ", S);
+  const int* ds = doc_bounds_ptr(doc_start, qkv, B, S, "doc_start");
   auto q = at::empty({B, S, Hq, D}, qkv.options());
   auto k = at::empty({B, S, Hkv, D}, qkv.options());
   auto v = at::empty({B, S, Hkv, D}, qkv.options());
   TOK_HIP_OK(tok_qkv_rope_fwd(qkv.data_ptr(), q.data_ptr(), k.data_ptr(),
                               v.data_ptr(), cos_tab.data_ptr<float>(),
                               sin_tab.data_ptr<float>(), tokens, (int)Hq,
-                              (int)Hkv, (int)D, S, current_stream()));
+                              (int)Hkv, (int)D, S, current_stream(), ds));
   return {q, k, v};
 }
 
 at::Tensor qkv_rope_bwd(at::Tensor dq, at::Tensor dk, at::Tensor dv,
-                        at::Tensor cos_tab, at::Tensor sin_tab) {
+                        at::Tensor cos_tab, at::Tensor sin_tab,
+                        c10::optional<at::Tensor> doc_start) {
   CHECK_BF16_CUDA(dq);
   CHECK_BF16_CUDA(dk);
   CHECK_BF16_CUDA(dv);
@@ -290,11 +312,12 @@ at::Tensor qkv_rope_bwd(at::Tensor dq, at::Tensor dk, at::Tensor dv,
   const long table_rows = cos_tab.numel() / (D / 2);
   TORCH_CHECK(table_rows >= S, "rope table has ", table_rows,
               " rows, sequence needs ", S);
+  const int* ds = doc_bounds_ptr(doc_start, dq, B, S, "doc_start");
   auto dqkv = at::empty({B, S, (Hq + 2 * Hkv) * D}, dq.options());
   TOK_HIP_OK(tok_qkv_rope_bwd(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
                               dqkv.data_ptr(), cos_tab.data_ptr<float>(),
                               sin_tab.data_ptr<float>(), tokens, (int)Hq,
-                              (int)Hkv, (int)D, S, current_stream()));
+                              (int)Hkv, (int)D, S, current_stream(), ds));
   return dqkv;
 }
 
@@ -391,8 +414,11 @@ void grad_norm_finalize_(at::Tensor partials, at::Tensor out, double inv_count,
 // q: [B,S,Hq,D], k/v: [B,S,Hkv,D] bf16 contiguous -> (o, lse[B,Hq,S] f32)
 // variant = 0: the v4 forward kernel (default); 1: the older v3, for A/B
 // timing and cross-checks in one process.
+// doc_start: optional packed-document bounds (query i sees keys
+// doc_start[b, i] .. i); causal variant 0 only.
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                 bool causal, int64_t variant) {
+                                 bool causal, int64_t variant,
+                                 c10::optional<at::Tensor> doc_start) {
   CHECK_BF16_CUDA(q);
   CHECK_BF16_CUDA(k);
   CHECK_BF16_CUDA(v);
@@ -402,6 +428,9 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
   TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == B && k.size(1) == S);
   TORCH_CHECK(variant == 0 || variant == 1, "attn_fwd variant must be 0 or 1");
+  const int* ds = doc_bounds_ptr(doc_start, q, B, S, "doc_start");
+  TORCH_CHECK(!ds || (causal && variant == 0),
+              "document bounds need causal=true and attn_fwd variant 0");
   auto o = at::empty_like(q);
   auto lse = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
   const int S_pad = (S + 63) / 64 * 64;
@@ -411,7 +440,7 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   TOK_HIP_OK(tok_attn_fwd(q.data_ptr(), k.data_ptr(), vt.data_ptr(),
                           o.data_ptr(), lse.data_ptr<float>(), B, S, Hq, Hkv,
                           D, S_pad, causal ? 1 : 0, current_stream(),
-                          (int)variant));
+                          (int)variant, ds));
   return {o, lse};
 }
 
@@ -421,13 +450,23 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
 // 0: the 4-wave dQ kernel; 2: the 8-wave kernel in plain block order.
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor o, at::Tensor lse, at::Tensor dout,
-                                 bool causal, bool split, int64_t dq_variant) {
+                                 bool causal, bool split, int64_t dq_variant,
+                                 c10::optional<at::Tensor> doc_start,
+                                 c10::optional<at::Tensor> doc_end) {
   CHECK_BF16_CUDA(q);
   CHECK_BF16_CUDA(dout);
   const int B = q.size(0), S = q.size(1), Hq = q.size(2), D = q.size(3);
   const int Hkv = k.size(2);
   TORCH_CHECK(dq_variant >= 0 && dq_variant <= 2,
               "attn_bwd dq_variant must be 0, 1 or 2");
+  // packed-document bounds: dQ masks by doc_start of its q rows, the fused
+  // dK+dV kernel by doc_end of its keys
+  const int* ds = doc_bounds_ptr(doc_start, q, B, S, "doc_start");
+  const int* de = doc_bounds_ptr(doc_end, q, B, S, "doc_end");
+  TORCH_CHECK((ds == nullptr) == (de == nullptr),
+              "attn_bwd takes doc_start and doc_end together");
+  TORCH_CHECK(!ds || (causal && !split && dq_variant == 1),
+              "document bounds need causal=true, split=false, dq_variant=1");
   auto dq = at::empty_like(q);
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
@@ -451,7 +490,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                           lse.data_ptr<float>(), dsum.data_ptr<float>(),
                           rc.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S,
                           Hq, Hkv, D, S_pad, causal ? 1 : 0, current_stream(),
-                          split ? 1 : 0, (int)dq_variant));
+                          split ? 1 : 0, (int)dq_variant, ds, de));
   return {dq, dk, dv};
 }
 
@@ -759,11 +798,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("mfma_probe", &mfma_probe, "MFMA 16x16x32 bf16 layout probe");
   mod.def("attn_fwd", &attn_fwd, "Flash attention forward (bf16, gfx950)",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
-          py::arg("variant") = 0);
+          py::arg("variant") = 0, py::arg("doc_start") = py::none());
   mod.def("attn_bwd", &attn_bwd, "Flash attention backward (bf16, gfx950)",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
           py::arg("lse"), py::arg("dout"), py::arg("causal"),
-          py::arg("split") = false, py::arg("dq_variant") = 1);
+          py::arg("split") = false, py::arg("dq_variant") = 1,
+          py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none());
   mod.def("ce_fwd", &ce_fwd, "Fused cross-entropy forward (bf16, gfx950)");
   mod.def("layernorm_fwd", &layernorm_fwd, "LayerNorm forward (bf16, gfx950)");
   mod.def("attn_decode", &attn_decode,
@@ -797,9 +837,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("swiglu_bwd", &swiglu_bwd,
           "Fused SwiGLU backward (bf16, gfx950)");
   mod.def("qkv_rope_fwd", &qkv_rope_fwd,
-          "Packed-QKV split + RoPE (bf16, gfx950)");
+          "Packed-QKV split + RoPE (bf16, gfx950)", py::arg("qkv"),
+          py::arg("cos_tab"), py::arg("sin_tab"), py::arg("Hq"),
+          py::arg("Hkv"), py::arg("D"), py::arg("doc_start") = py::none());
   mod.def("qkv_rope_bwd", &qkv_rope_bwd,
-          "Packed-QKV gather + inverse RoPE (bf16, gfx950)");
+          "Packed-QKV gather + inverse RoPE (bf16, gfx950)", py::arg("dq"),
+          py::arg("dk"), py::arg("dv"), py::arg("cos_tab"),
+          py::arg("sin_tab"), py::arg("doc_start") = py::none());
   mod.def("rope", &rope, "Rotary embedding rotate-half (bf16, gfx950)");
   mod.def("adamw_", &adamw_, "Fused AdamW on a flat bucket (gfx950)",
           py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"),

@@ -15,6 +15,12 @@
 // cos/sin: host-precomputed fp32 [>= S, D/2] (no device trig — guide:
 // memory-bound op must not become VALU-bound). position = token % S; the
 // caller checks that the table has at least S rows.
+//
+// Packed documents (DOC): doc_start is int32 [tokens]; a token's position
+// is counted from the first token of its document, s - doc_start[b, s],
+// and nothing else changes, so a document's rows come out with the bits
+// it gets as a row of its own. The value is clamped into [0, s]: a
+// malformed tensor gives a wrong phase, never a table row out of range.
 #include "common.h"
 
 namespace {
@@ -24,6 +30,7 @@ constexpr int BLOCK = 256;
 // Work item = one 8-wide vec of the FIRST half of one head row (its
 // partner vec in the second half is handled by the same thread, as in
 // rope_kernel). rows span tokens*heads_total.
+template <bool DOC>
 __global__ void qkv_rope_kernel(const bf16x8* __restrict__ qkv,
                                 bf16x8* __restrict__ q,
                                 bf16x8* __restrict__ k,
@@ -31,7 +38,8 @@ __global__ void qkv_rope_kernel(const bf16x8* __restrict__ qkv,
                                 const float* __restrict__ tab_cos,
                                 const float* __restrict__ tab_sin,
                                 long tokens, int Hq, int Hkv, int hv /* (D/2)/8 */,
-                                long S, float sign) {
+                                long S, float sign,
+                                const int* __restrict__ doc_start) {
   const int heads_total = Hq + 2 * Hkv;
   const int dv8 = hv * 2;  // vecs per head (D/8)
   const long nwork = tokens * heads_total * hv;
@@ -57,7 +65,8 @@ __global__ void qkv_rope_kernel(const bf16x8* __restrict__ qkv,
       rot = false;
     }
     if (rot) {
-      const long pos = token % S;
+      long pos = token % S;
+      if (DOC) pos -= max(0L, min((long)doc_start[token], pos));
       const float* cosr = tab_cos + pos * (hv * 8);
       const float* sinr = tab_sin + pos * (hv * 8);
       bf16x8 o1, o2;
@@ -80,6 +89,7 @@ __global__ void qkv_rope_kernel(const bf16x8* __restrict__ qkv,
 }
 
 // Mirror: gather dq/dk/dv into packed dqkv, inverse-rotating dq/dk.
+template <bool DOC>
 __global__ void qkv_rope_bwd_kernel(const bf16x8* __restrict__ dq,
                                     const bf16x8* __restrict__ dk,
                                     const bf16x8* __restrict__ dv,
@@ -87,7 +97,8 @@ __global__ void qkv_rope_bwd_kernel(const bf16x8* __restrict__ dq,
                                     const float* __restrict__ tab_cos,
                                     const float* __restrict__ tab_sin,
                                     long tokens, int Hq, int Hkv, int hv,
-                                    long S) {
+                                    long S,
+                                    const int* __restrict__ doc_start) {
   const int heads_total = Hq + 2 * Hkv;
   const int dv8 = hv * 2;
   const long nwork = tokens * heads_total * hv;
@@ -113,7 +124,8 @@ __global__ void qkv_rope_bwd_kernel(const bf16x8* __restrict__ dq,
     bf16x8 x2 = src[c + hv];
     bf16x8* dst = dqkv + (token * heads_total + h) * dv8;
     if (rot) {
-      const long pos = token % S;
+      long pos = token % S;
+      if (DOC) pos -= max(0L, min((long)doc_start[token], pos));
       const float* cosr = tab_cos + pos * (hv * 8);
       const float* sinr = tab_sin + pos * (hv * 8);
       bf16x8 o1, o2;
@@ -142,15 +154,21 @@ extern "C" {
 hipError_t tok_qkv_rope_fwd(const void* qkv, void* q, void* k, void* v,
                             const float* cos_tab, const float* sin_tab,
                             long tokens, int Hq, int Hkv, int D,
-                            long S, hipStream_t stream) {
+                            long S, hipStream_t stream,
+                            const int* doc_start) {
   const int hv = (D / 2) / 8;
   const long nwork = tokens * (long)(Hq + 2 * Hkv) * hv;
   long grid = (nwork + BLOCK - 1) / BLOCK;
   if (grid > 8192) grid = 8192;
   if (grid < 1) grid = 1;
-  qkv_rope_kernel<<<(int)grid, BLOCK, 0, stream>>>(
-      (const bf16x8*)qkv, (bf16x8*)q, (bf16x8*)k, (bf16x8*)v, cos_tab,
-      sin_tab, tokens, Hq, Hkv, hv, S, 1.0f);
+  if (doc_start)
+    qkv_rope_kernel<true><<<(int)grid, BLOCK, 0, stream>>>(
+        (const bf16x8*)qkv, (bf16x8*)q, (bf16x8*)k, (bf16x8*)v, cos_tab,
+        sin_tab, tokens, Hq, Hkv, hv, S, 1.0f, doc_start);
+  else
+    qkv_rope_kernel<false><<<(int)grid, BLOCK, 0, stream>>>(
+        (const bf16x8*)qkv, (bf16x8*)q, (bf16x8*)k, (bf16x8*)v, cos_tab,
+        sin_tab, tokens, Hq, Hkv, hv, S, 1.0f, nullptr);
   return hipGetLastError();
 }
 
@@ -158,15 +176,20 @@ hipError_t tok_qkv_rope_bwd(const void* dq, const void* dk, const void* dv,
                             void* dqkv, const float* cos_tab,
                             const float* sin_tab, long tokens, int Hq,
                             int Hkv, int D, long S,
-                            hipStream_t stream) {
+                            hipStream_t stream, const int* doc_start) {
   const int hv = (D / 2) / 8;
   const long nwork = tokens * (long)(Hq + 2 * Hkv) * hv;
   long grid = (nwork + BLOCK - 1) / BLOCK;
   if (grid > 8192) grid = 8192;
   if (grid < 1) grid = 1;
-  qkv_rope_bwd_kernel<<<(int)grid, BLOCK, 0, stream>>>(
-      (const bf16x8*)dq, (const bf16x8*)dk, (const bf16x8*)dv, (bf16x8*)dqkv,
-      cos_tab, sin_tab, tokens, Hq, Hkv, hv, S);
+  if (doc_start)
+    qkv_rope_bwd_kernel<true><<<(int)grid, BLOCK, 0, stream>>>(
+        (const bf16x8*)dq, (const bf16x8*)dk, (const bf16x8*)dv,
+        (bf16x8*)dqkv, cos_tab, sin_tab, tokens, Hq, Hkv, hv, S, doc_start);
+  else
+    qkv_rope_bwd_kernel<false><<<(int)grid, BLOCK, 0, stream>>>(
+        (const bf16x8*)dq, (const bf16x8*)dk, (const bf16x8*)dv,
+        (bf16x8*)dqkv, cos_tab, sin_tab, tokens, Hq, Hkv, hv, S, nullptr);
   return hipGetLastError();
 }
 }
