@@ -358,8 +358,11 @@ def test_rmsnorm_residual_fused():
 
 
 def test_llama_tiny_fused_block_matches_cpu():
-    """End-to-end: tiny model loss/grads on GPU (all fused kernels) match
-    the CPU fp32 path within bf16 tolerance."""
+    """End-to-end: the tiny model's LOSS on the GPU (all fused kernels)
+    matches the CPU fp32 path within 0.05. The loss only: no gradient is
+    looked at here. Logits, loss and every parameter gradient of the HIP
+    path are held to an independent fp64 model in
+    test_model_oracle_gpu.py."""
     from torch_on_k8s_amd.models.llama import LlamaModel, get_config
     torch.manual_seed(0)
     cfg = get_config("llama-tiny")

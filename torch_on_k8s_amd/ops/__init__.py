@@ -39,14 +39,22 @@ def _require_ext(op: str):
     return _C
 
 
+def _wide(t: torch.Tensor) -> torch.Tensor:
+    """The type the CPU reference paths compute in: fp32 for bf16, fp16 and
+    fp32 inputs, and fp64 for fp64 inputs, which are never narrowed (a
+    .double() model on the CPU path is then the model in fp64, which is what
+    tests/model_oracle.py is held against)."""
+    return t if t.dtype == torch.float64 else t.float()
+
+
 # --------------------------------------------------------------------------
 # RMSNorm
 # --------------------------------------------------------------------------
 def rmsnorm_ref(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
     """fp32 reference: y = x * w / sqrt(mean(x^2) + eps)."""
-    xf = x.float()
+    xf = _wide(x)
     r = torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
-    return (xf * r * w.float()).to(x.dtype)
+    return (xf * r * _wide(w)).to(x.dtype)
 
 
 class _RMSNormFn(torch.autograd.Function):
@@ -55,9 +63,9 @@ class _RMSNormFn(torch.autograd.Function):
         if x.is_cuda:
             y, invr = _require_ext("rmsnorm").rmsnorm_fwd(x, w, eps)
         else:
-            xf = x.float()
+            xf = _wide(x)
             invr = torch.rsqrt(xf.pow(2).mean(-1) + eps).reshape(-1)
-            y = (xf * invr.view(*x.shape[:-1], 1) * w.float()).to(x.dtype)
+            y = (xf * invr.view(*x.shape[:-1], 1) * _wide(w)).to(x.dtype)
         ctx.save_for_backward(x, w, invr)
         return y
 
@@ -68,7 +76,7 @@ class _RMSNormFn(torch.autograd.Function):
         if x.is_cuda:
             dx, dw = _C.rmsnorm_bwd(x, w, dy, invr)
         else:
-            xf, wf, dyf = x.float(), w.float(), dy.float()
+            xf, wf, dyf = _wide(x), _wide(w), _wide(dy)
             H = x.shape[-1]
             r = invr.view(*x.shape[:-1], 1)
             c = (dyf * wf * xf).sum(-1, keepdim=True)
@@ -94,29 +102,34 @@ class _RMSNormResFn(torch.autograd.Function):
                 x, res, w, eps)
         else:
             xr = x + res if res is not None else x
-            xf = xr.float()
+            xf = _wide(xr)
             invr = torch.rsqrt(xf.pow(2).mean(-1) + eps).reshape(-1)
-            y = (xf * invr.view(*xr.shape[:-1], 1) * w.float()).to(x.dtype)
+            y = (xf * invr.view(*xr.shape[:-1], 1) * _wide(w)).to(x.dtype)
         ctx.save_for_backward(xr, w, invr)
         ctx.has_res = res is not None
+        # an output nobody used (the final norm's xr) arrives in backward
+        # as None, not as a zero tensor to fill, read and add
+        ctx.set_materialize_grads(False)
         return y, xr
 
     @staticmethod
     def backward(ctx, dy, dxr):
         xr, w, invr = ctx.saved_tensors
+        if dy is None:      # only xr was used: the norm itself had no reader
+            dy = torch.zeros_like(xr)
         dy = dy.contiguous()
         if dxr is not None:
             dxr = dxr.contiguous()
         if xr.is_cuda:
             dx, dw = _C.rmsnorm_res_bwd(xr, w, dy, dxr, invr)
         else:
-            xf, wf, dyf = xr.float(), w.float(), dy.float()
+            xf, wf, dyf = _wide(xr), _wide(w), _wide(dy)
             H = xr.shape[-1]
             r = invr.view(*xr.shape[:-1], 1)
             c = (dyf * wf * xf).sum(-1, keepdim=True)
             dx = r * (wf * dyf - xf * (r * r / H) * c)
             if dxr is not None:  # added in fp32, one rounding, as the kernel
-                dx = dx + dxr.float()
+                dx = dx + _wide(dxr)
             dx = dx.to(xr.dtype)
             dw = (dyf * xf * r).reshape(-1, H).sum(0)
         dres = dx if ctx.has_res else None
@@ -143,7 +156,7 @@ def rope_ref(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
     if cos.shape[0] < S or sin.shape[0] < S:
         raise ValueError(
             f"rope table has {cos.shape[0]} rows, sequence needs {S}")
-    xf = x.float()
+    xf = _wide(x)
     x1, x2 = xf[..., : D // 2], xf[..., D // 2:]
     if doc_start is None:
         cs = cos[:S].reshape(1, S, 1, D // 2)
@@ -260,7 +273,7 @@ def qkv_rope(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
 def swiglu_ref(gu: torch.Tensor) -> torch.Tensor:
     """fp32 reference: silu(gate) * up over packed [..., 2I]."""
     I = gu.shape[-1] // 2
-    g, u = gu.float().split(I, dim=-1)
+    g, u = _wide(gu).split(I, dim=-1)
     return (torch.nn.functional.silu(g) * u).to(gu.dtype)
 
 
@@ -278,11 +291,11 @@ class _SwiGLUFn(torch.autograd.Function):
         if gu.is_cuda:
             return _C.swiglu_bwd(dout.contiguous(), gu)
         I = gu.shape[-1] // 2
-        g, u = gu.float().split(I, dim=-1)
+        g, u = _wide(gu).split(I, dim=-1)
         sg = torch.sigmoid(g)
         silu = g * sg
         dsilu = sg * (1 + g * (1 - sg))
-        df = dout.float()
+        df = _wide(dout)
         return torch.cat([df * u * dsilu, df * silu], dim=-1).to(gu.dtype)
 
 
@@ -470,9 +483,9 @@ def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
     rep = Hq // Hkv
-    qf = q.float().permute(0, 2, 1, 3)  # B,Hq,S,D
-    kf = k.float().permute(0, 2, 1, 3).repeat_interleave(rep, dim=1)
-    vf = v.float().permute(0, 2, 1, 3).repeat_interleave(rep, dim=1)
+    qf = _wide(q).permute(0, 2, 1, 3)  # B,Hq,S,D
+    kf = _wide(k).permute(0, 2, 1, 3).repeat_interleave(rep, dim=1)
+    vf = _wide(v).permute(0, 2, 1, 3).repeat_interleave(rep, dim=1)
     s = torch.matmul(qf, kf.transpose(-1, -2)) / (D ** 0.5)
     if causal:
         mask = torch.triu(torch.ones(S, S, dtype=torch.bool, device=q.device), 1)
@@ -779,12 +792,12 @@ class _LayerNormFn(torch.autograd.Function):
         if x.is_cuda:
             y, mu, rstd = _require_ext("layernorm").layernorm_fwd(x, w, b, eps)
         else:
-            xf = x.float()
+            xf = _wide(x)
             mu = xf.mean(-1)
             var = xf.var(-1, unbiased=False)
             rstd = torch.rsqrt(var + eps)
-            y = (((xf - mu.unsqueeze(-1)) * rstd.unsqueeze(-1)) * w.float() +
-                 b.float()).to(x.dtype)
+            y = (((xf - mu.unsqueeze(-1)) * rstd.unsqueeze(-1)) * _wide(w) +
+                 _wide(b)).to(x.dtype)
             mu, rstd = mu.reshape(-1), rstd.reshape(-1)
         ctx.save_for_backward(x, w, mu, rstd)
         return y
@@ -797,7 +810,7 @@ class _LayerNormFn(torch.autograd.Function):
             dx, dw, db = _C.layernorm_bwd(x, w, dy, mu, rstd)
         else:
             H = x.shape[-1]
-            xf, wf, dyf = x.float(), w.float(), dy.float()
+            xf, wf, dyf = _wide(x), _wide(w), _wide(dy)
             muv = mu.view(*x.shape[:-1], 1)
             rs = rstd.view(*x.shape[:-1], 1)
             xhat = (xf - muv) * rs
@@ -842,7 +855,7 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         return _FusedCEFn.apply(logits.contiguous().view(-1, logits.shape[-1]),
                                 labels.reshape(-1).int())
     return torch.nn.functional.cross_entropy(
-        logits.float().view(-1, logits.shape[-1]), labels.reshape(-1))
+        _wide(logits).view(-1, logits.shape[-1]), labels.reshape(-1))
 
 
 # --------------------------------------------------------------------------
