@@ -56,6 +56,16 @@ class TrainerConfig:
     data_dtype: str = "uint16"      # token width in data_path: uint16|uint32
     doc_eos_id: int | None = None   # packed documents: attention and RoPE
                                     # restart after every token with this id
+    label_ignore_index: int = -100  # label value that keeps a token out of
+                                    # the loss (outside [0, vocab))
+    mask_doc_end_labels: bool = False  # needs doc_eos_id: the label at every
+                                       # EOS input (the next document's first
+                                       # token) becomes label_ignore_index
+    z_loss: float = 0.0             # adds z_loss * lse^2 per counted token
+
+    def __post_init__(self):
+        if self.mask_doc_end_labels and self.doc_eos_id is None:
+            raise ValueError("mask_doc_end_labels needs doc_eos_id")
 
     def to_dict(self):
         d = asdict(self)
@@ -144,11 +154,21 @@ class Trainer:
     def _loss(self, inp, lab):
         """Forward of one micro-batch. With doc_eos_id the document bounds
         are derived from the batch on the device (no host sync, so also
-        inside the captured step) and handed to the model."""
-        if self.cfg.doc_eos_id is None:
-            return self.fb(inp, lab)
-        ds, de = ops.doc_bounds(inp, self.cfg.doc_eos_id)
-        return self.fb(inp, lab, doc_start=ds, doc_end=de)
+        inside the captured step) and handed to the model. With
+        mask_doc_end_labels the label of every EOS input is masked the same
+        way; the loss is then the mean over this micro-batch's other tokens."""
+        cfg = self.cfg
+        kw = {}
+        if cfg.mask_doc_end_labels:
+            lab = torch.where(inp == cfg.doc_eos_id, cfg.label_ignore_index,
+                              lab)
+            kw["ignore_index"] = cfg.label_ignore_index
+        if cfg.z_loss:
+            kw["z_loss"] = cfg.z_loss
+        if cfg.doc_eos_id is None:
+            return self.fb(inp, lab, **kw)
+        ds, de = ops.doc_bounds(inp, cfg.doc_eos_id)
+        return self.fb(inp, lab, doc_start=ds, doc_end=de, **kw)
 
     def train_step(self, sync: bool = True):
         """One full step: data -> fwd -> bwd (overlapped RCCL all-reduce)

@@ -131,7 +131,8 @@ class GPT2Model(nn.Module):
     def forward(self, input_ids: torch.Tensor,
                 labels: torch.Tensor | None = None,
                 doc_start: torch.Tensor | None = None,
-                doc_end: torch.Tensor | None = None):
+                doc_end: torch.Tensor | None = None,
+                ignore_index: int | None = None, z_loss: float = 0.0):
         if doc_start is not None or doc_end is not None:
             raise NotImplementedError(
                 "GPT-2 has no packed-document path: its learned positions "
@@ -149,7 +150,8 @@ class GPT2Model(nn.Module):
         logits = self.lm_head(x)
         if labels is None:
             return logits
-        return ops.cross_entropy(logits, labels)
+        return ops.cross_entropy(logits, labels, ignore_index=ignore_index,
+                                 z_loss=z_loss)
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,

@@ -248,14 +248,18 @@ class LlamaModel(nn.Module):
     def forward(self, input_ids: torch.Tensor,
                 labels: torch.Tensor | None = None,
                 doc_start: torch.Tensor | None = None,
-                doc_end: torch.Tensor | None = None):
+                doc_end: torch.Tensor | None = None,
+                ignore_index: int | None = None, z_loss: float = 0.0):
         """doc_start / doc_end: packed-document bounds of input_ids
-        (ops.doc_bounds). Labels are not masked at document ends."""
+        (ops.doc_bounds). ignore_index / z_loss: as ops.cross_entropy;
+        tokens whose label is ignore_index are left out of the loss, whose
+        mean is over the rest."""
         x = self.forward_hidden(input_ids, doc_start, doc_end)
         logits = ops.linear(x, self.lm_head.weight)
         if labels is None:
             return logits
-        return ops.cross_entropy(logits, labels)
+        return ops.cross_entropy(logits, labels, ignore_index=ignore_index,
+                                 z_loss=z_loss)
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 32,

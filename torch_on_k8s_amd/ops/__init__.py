@@ -848,14 +848,83 @@ class _FusedCEFn(torch.autograd.Function):
         return dlogits, None
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+class _MaskedCEFn(torch.autograd.Function):
+    """Mean over the counted rows (0 <= label < V) of CE + z * lse^2. The
+    count never leaves the device: the forward leaves 1/count there and the
+    backward kernel reads it, so the pair captures into a hipGraph and a
+    replay follows new labels."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, z, inplace):
+        loss, lse, inv_count, _ = _require_ext("cross_entropy").ce_fwd_masked(
+            logits, labels, z)
+        ctx.save_for_backward(logits, labels, lse, inv_count)
+        ctx.z, ctx.inplace = z, inplace
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        logits, labels, lse, inv_count = ctx.saved_tensors
+        dlogits = _C.ce_bwd_masked(
+            logits, labels, lse, grad_out.float().reshape(()).contiguous(),
+            inv_count, ctx.z, logits if ctx.inplace else None)
+        return dlogits, None, None, None
+
+
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor,
+                  ignore_index: int | None = None, z_loss: float = 0.0,
+                  inplace_backward: bool = False) -> torch.Tensor:
     """Mean next-token CE. GPU bf16: fused single-pass kernels (one logits
-    read fwd, one read + bf16 grad write bwd). CPU: eager fp32."""
+    read fwd, one read + bf16 grad write bwd). CPU: eager fp32.
+
+    With the three options at their defaults every row counts and every label
+    must lie in [0, V). Otherwise GPU bf16 runs the masked kernels, and every
+    other tensor the same formula in eager fp32 torch ops on its own device:
+
+    ignore_index: rows whose label has this value (outside [0, V)) are left
+      out of the loss and get a zero gradient; the mean is over the rows that
+      count, and a batch in which none counts gives 0, not NaN. The GPU
+      kernels treat every label outside [0, V) as ignored and never read such
+      a row (its logits may hold anything); the CPU path raises ValueError
+      for an out-of-range label other than ignore_index.
+    z_loss: adds z_loss * lse^2 per counted row (the PaLM auxiliary term).
+    inplace_backward: the gradient is written over the logits and returned
+      in their storage, which saves one [rows, V] buffer. The logits are dead
+      after backward(): nothing may read them again, and a second backward
+      through the same graph is wrong. GPU bf16 only; the eager path ignores it.
+
+    No GPU path syncs with the host, so all of them can be captured."""
+    V = logits.shape[-1]
+    if ignore_index is None and z_loss == 0.0 and not inplace_backward:
+        if logits.is_cuda and logits.dtype == torch.bfloat16:
+            return _FusedCEFn.apply(logits.contiguous().view(-1, V),
+                                    labels.reshape(-1).int())
+        return torch.nn.functional.cross_entropy(
+            _wide(logits).view(-1, V), labels.reshape(-1))
+    if ignore_index is not None and 0 <= ignore_index < V:
+        raise ValueError(
+            f"ignore_index {ignore_index} names a class: it must lie outside "
+            f"[0, {V})")
     if logits.is_cuda and logits.dtype == torch.bfloat16:
-        return _FusedCEFn.apply(logits.contiguous().view(-1, logits.shape[-1]),
-                                labels.reshape(-1).int())
-    return torch.nn.functional.cross_entropy(
-        _wide(logits).view(-1, logits.shape[-1]), labels.reshape(-1))
+        return _MaskedCEFn.apply(logits.contiguous().view(-1, V),
+                                 labels.reshape(-1).int().contiguous(),
+                                 float(z_loss), bool(inplace_backward))
+    lab = labels.reshape(-1).long()
+    valid = (lab >= 0) & (lab < V)
+    if not logits.is_cuda:   # reading the labels on the host is free here
+        stray = ~valid if ignore_index is None \
+            else ~valid & (lab != ignore_index)
+        if bool(stray.any()):
+            raise ValueError(f"labels outside [0, {V}) other than "
+                             f"ignore_index={ignore_index}")
+    # ignored rows are not read: whatever they hold becomes 0 first
+    x = _wide(logits).view(-1, V).masked_fill(~valid.unsqueeze(1), 0.0)
+    total = torch.nn.functional.cross_entropy(
+        x, torch.where(valid, lab, -100), ignore_index=-100, reduction="sum")
+    if z_loss != 0.0:
+        lse = torch.logsumexp(x, dim=-1)
+        total = total + z_loss * (lse * lse * valid).sum()
+    return total / valid.sum().clamp(min=1)
 
 
 # --------------------------------------------------------------------------

@@ -113,6 +113,15 @@ hipError_t tok_ce_fwd(const void* logits, const int* labels, float* loss,
 hipError_t tok_ce_bwd(const void* logits, const int* labels, const float* lse,
                       const float* gscale, void* dlogits, long rows, int V,
                       hipStream_t stream);
+int tok_ce_masked_blocks(long rows);
+hipError_t tok_ce_fwd_masked(const void* logits, const int* labels, float* lse,
+                             float* part_sum, int* part_cnt, float* out,
+                             int* count, long rows, int V, float z,
+                             hipStream_t stream);
+hipError_t tok_ce_bwd_masked(const void* logits, const int* labels,
+                             const float* lse, const float* grad_out,
+                             const float* inv_count, void* dlogits, long rows,
+                             int V, float z, hipStream_t stream);
 }
 
 namespace {
@@ -703,6 +712,77 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor labels, at::Tensor lse,
   return dlogits;
 }
 
+// Masked CE: a row counts iff 0 <= label < V. Returns (loss, lse, inv_count,
+// count): loss and inv_count fp32 scalars, count an int32 scalar, all left on
+// the device (the launch geometry depends on the shapes alone, so the call
+// captures and a replay follows new labels).
+std::vector<at::Tensor> ce_fwd_masked(at::Tensor logits, at::Tensor labels,
+                                      double z) {
+  CHECK_BF16_CUDA(logits);
+  TORCH_CHECK(labels.scalar_type() == at::kInt && labels.is_cuda() &&
+                  labels.is_contiguous(),
+              "labels must be a contiguous int32 GPU tensor");
+  const long V = logits.size(-1);
+  TORCH_CHECK(V >= 8 && V % 8 == 0, "vocab must be a multiple of 8");
+  const long rows = logits.numel() / V;
+  TORCH_CHECK(labels.numel() == rows, "labels must hold one entry per row");
+  const int nb = tok_ce_masked_blocks(rows);
+  auto f32 = logits.options().dtype(at::kFloat);
+  auto i32 = logits.options().dtype(at::kInt);
+  auto lse = at::empty({rows}, f32);
+  auto part_sum = at::empty({nb}, f32);
+  auto part_cnt = at::empty({nb}, i32);
+  auto out = at::empty({2}, f32);
+  auto count = at::empty({}, i32);
+  TOK_HIP_OK(tok_ce_fwd_masked(logits.data_ptr(), labels.data_ptr<int>(),
+                               lse.data_ptr<float>(),
+                               part_sum.data_ptr<float>(),
+                               part_cnt.data_ptr<int>(), out.data_ptr<float>(),
+                               count.data_ptr<int>(), rows, (int)V, (float)z,
+                               current_stream()));
+  return {out.select(0, 0), lse, out.select(0, 1), count};
+}
+
+// out: logits itself (the gradient overwrites the logits), or any other bf16
+// tensor of its shape that does not overlap it; absent: a fresh tensor.
+// grad_out and inv_count are fp32 device scalars.
+at::Tensor ce_bwd_masked(at::Tensor logits, at::Tensor labels, at::Tensor lse,
+                         at::Tensor grad_out, at::Tensor inv_count, double z,
+                         c10::optional<at::Tensor> out) {
+  CHECK_BF16_CUDA(logits);
+  TORCH_CHECK(labels.scalar_type() == at::kInt && labels.is_cuda() &&
+                  labels.is_contiguous(),
+              "labels must be a contiguous int32 GPU tensor");
+  const long V = logits.size(-1);
+  TORCH_CHECK(V >= 8 && V % 8 == 0, "vocab must be a multiple of 8");
+  const long rows = logits.numel() / V;
+  TORCH_CHECK(labels.numel() == rows, "labels must hold one entry per row");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
+                  lse.is_contiguous() && lse.numel() == rows,
+              "lse must be a contiguous fp32 GPU tensor, one entry per row");
+  const float* go = dev_f32_scalar(grad_out, "grad_out");
+  const float* ic = dev_f32_scalar(inv_count, "inv_count");
+  at::Tensor dlogits;
+  if (out.has_value()) {
+    dlogits = *out;
+    CHECK_BF16_CUDA(dlogits);
+    TORCH_CHECK(dlogits.sizes() == logits.sizes(),
+                "out must have the shape of logits");
+    const char* a = (const char*)logits.data_ptr();
+    const char* b = (const char*)dlogits.data_ptr();
+    const long nbytes = logits.numel() * 2;
+    TORCH_CHECK(a == b || a + nbytes <= b || b + nbytes <= a,
+                "out must be logits itself or not overlap it");
+  } else {
+    dlogits = at::empty_like(logits);
+  }
+  TOK_HIP_OK(tok_ce_bwd_masked(logits.data_ptr(), labels.data_ptr<int>(),
+                               lse.data_ptr<float>(), go, ic,
+                               dlogits.data_ptr(), rows, (int)V, (float)z,
+                               current_stream()));
+  return dlogits;
+}
+
 at::Tensor mfma_probe(at::Tensor A, at::Tensor B) {
   CHECK_BF16_CUDA(A);
   CHECK_BF16_CUDA(B);
@@ -823,6 +903,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("u") = py::none());
   mod.def("layernorm_bwd", &layernorm_bwd, "LayerNorm backward (bf16, gfx950)");
   mod.def("ce_bwd", &ce_bwd, "Fused cross-entropy backward (bf16, gfx950)");
+  mod.def("ce_fwd_masked", &ce_fwd_masked,
+          "Masked cross-entropy forward with z-loss: (loss, lse, inv_count, "
+          "count) (bf16, gfx950)",
+          py::arg("logits"), py::arg("labels"), py::arg("z"));
+  mod.def("ce_bwd_masked", &ce_bwd_masked,
+          "Masked cross-entropy backward, optionally in place (bf16, gfx950)",
+          py::arg("logits"), py::arg("labels"), py::arg("lse"),
+          py::arg("grad_out"), py::arg("inv_count"), py::arg("z"),
+          py::arg("out") = py::none());
   mod.def("rmsnorm_fwd", &rmsnorm_fwd, "RMSNorm forward (bf16, gfx950)");
   mod.def("rmsnorm_bwd", &rmsnorm_bwd, "RMSNorm backward (bf16, gfx950)");
   mod.def("rmsnorm_res_fwd", &rmsnorm_res_fwd,
