@@ -379,7 +379,9 @@ class LlamaModel(nn.Module):
                         use_graph: bool | None = None,
                         pad_token_id: int = 0, *,
                         temperature=0.0, top_k=0, top_p=1.0,
-                        seed=None) -> list[torch.Tensor]:
+                        seed=None,
+                        prefill_chunk: int | None = None
+                        ) -> list[torch.Tensor]:
         """Generation for prompts of different lengths (each a 1-D id
         tensor or a list of ids, length >= 1). Returns one 1-D tensor per
         sequence: the prompt followed by its new tokens, ending at the
@@ -400,7 +402,17 @@ class LlamaModel(nn.Module):
         reads before it overwrites them. Decode keeps per-sequence
         lengths on the device (ops.qkv_rope_append_ +
         ops.attention_decode_ragged), so one captured step serves every
-        sequence whatever its length."""
+        sequence whatever its length.
+
+        prefill_chunk=N (>= 1) prefills through the cache instead, in
+        ceil(S0 / N) chunks of N tokens per sequence: each chunk is appended
+        by ops.qkv_rope_append_chunk_ and attends to the cache by
+        ops.attention_extend, with per-sequence positions and lengths on
+        the device, so no pad key is ever written or read and the
+        activations are [B, N] wide. None (the default) is the padded
+        prefill above."""
+        if prefill_chunk is not None and int(prefill_chunk) < 1:
+            raise ValueError("prefill_chunk must be >= 1 or None")
         cfg = self.cfg
         dev = self.embed_tokens.weight.device
         dtype = self.embed_tokens.weight.dtype
@@ -463,17 +475,45 @@ class LlamaModel(nn.Module):
               for _ in self.layers]
         cos, sin = build_rope_table(cfg, Tmax, dev)
 
-        # prefill over the padded rectangle
-        x = self.embed_tokens(input_ids)
-        cs0, sn0 = cos[:S0].contiguous(), sin[:S0].contiguous()
-        for i, blk in enumerate(self.layers):
-            q, k, v = blk.attn.project_qkv(blk.input_norm(x), cs0, sn0)
-            kc[i][:, :S0] = k
-            vc[i][:, :S0] = v
-            o = ops.attention(q, k, v, causal=True)
-            x = x + blk.attn.o_proj(o.reshape(B, S0, Hq * D))
-            x = x + blk.mlp(blk.post_attn_norm(x))
-        last = x[torch.arange(B, device=dev), lens0 - 1].unsqueeze(1)
+        if prefill_chunk is None:
+            # prefill over the padded rectangle
+            x = self.embed_tokens(input_ids)
+            cs0, sn0 = cos[:S0].contiguous(), sin[:S0].contiguous()
+            for i, blk in enumerate(self.layers):
+                q, k, v = blk.attn.project_qkv(blk.input_norm(x), cs0, sn0)
+                kc[i][:, :S0] = k
+                vc[i][:, :S0] = v
+                o = ops.attention(q, k, v, causal=True)
+                x = x + blk.attn.o_proj(o.reshape(B, S0, Hq * D))
+                x = x + blk.mlp(blk.post_attn_norm(x))
+            last = x[torch.arange(B, device=dev), lens0 - 1].unsqueeze(1)
+        else:
+            # prefill through the cache, N tokens per sequence at a time
+            N = int(prefill_chunk)
+            len32 = lens0.to(torch.int32)
+            last = torch.zeros(B, 1, cfg.hidden_size, dtype=dtype, device=dev)
+            rows = torch.arange(B, device=dev)
+            for c0 in range(0, S0, N):
+                ids = input_ids[:, c0:c0 + N]
+                if ids.shape[1] < N:  # the last chunk: same shape, dead tail
+                    ids = torch.nn.functional.pad(ids, (0, N - ids.shape[1]),
+                                                  value=pad_token_id)
+                cpos = torch.full((B,), c0, dtype=torch.int32, device=dev)
+                cql = (len32 - c0).clamp(0, N)
+                clen = len32.clamp(max=c0 + N)
+                x = self.embed_tokens(ids)
+                for i, blk in enumerate(self.layers):
+                    qkv = blk.attn.qkv_proj(blk.input_norm(x))
+                    q = ops.qkv_rope_append_chunk_(qkv, cos, sin, cpos, cql,
+                                                   kc[i], vc[i], Hq, Hkv, D)
+                    o = ops.attention_extend(q, kc[i], vc[i], clen, cql)
+                    x = x + blk.attn.o_proj(o.reshape(B, N, Hq * D))
+                    x = x + blk.mlp(blk.post_attn_norm(x))
+                # the chunk that holds a sequence's last prompt token
+                at = lens0 - 1 - c0
+                here = ((at >= 0) & (at < N)).view(B, 1, 1)
+                last = torch.where(here, x[rows, at.clamp(0, N - 1)]
+                                   .unsqueeze(1), last)
         first = pick(self.lm_head(self.norm(last))[:, -1], lens0).unsqueeze(1)
 
         # Decode state, all on the device. token_buf holds the token to

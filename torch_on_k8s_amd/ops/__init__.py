@@ -687,6 +687,124 @@ def qkv_rope_append_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
 
 
 # --------------------------------------------------------------------------
+# Chunked ragged prefill: Tq new tokens per sequence over the KV cache
+# --------------------------------------------------------------------------
+_EXTEND_TARGET_BLOCKS = 512    # about two blocks per CU (256 CUs)
+_EXTEND_MAX_CHUNK = 2048       # keys: the decode rule's constants, unmoved
+_EXTEND_MAX_SPLITS = 32
+_EXTEND_TILE = 64              # keys per tile = packed q rows per block
+
+
+def extend_splits(B: int, Hkv: int, Tq: int, R: int, Tmax: int) -> int:
+    """Default split count of attention_extend. Depends on shapes alone. The
+    decode rule with the row tiles counted in: about two blocks per CU, no
+    chunk above 2048 keys, none below 64, at most 32 splits. From the sweep
+    in profiles/attn_extend.log: once the row tiles alone fill the target
+    there is one split whatever Tmax (every extra split re-reads q and adds a
+    partial per row: 8-15 % slower at Tq = 256)."""
+    blocks = max(1, B * Hkv * -(-Tq * R // _EXTEND_TILE))
+    if blocks >= _EXTEND_TARGET_BLOCKS:
+        return 1
+    want = max(_EXTEND_TARGET_BLOCKS // blocks, -(-Tmax // _EXTEND_MAX_CHUNK))
+    return max(1, min(want, Tmax // _EXTEND_TILE, _EXTEND_MAX_SPLITS))
+
+
+def extend_chunk(Tmax: int, num_splits: int) -> int:
+    """Keys per split, a multiple of 64 and never below 64."""
+    per = -(-Tmax // max(1, num_splits))
+    return max(1, -(-per // _EXTEND_TILE)) * _EXTEND_TILE
+
+
+@torch.no_grad()
+def attention_extend(q: torch.Tensor, kcache: torch.Tensor,
+                     vcache: torch.Tensor, lens: torch.Tensor,
+                     qlens: torch.Tensor, *,
+                     num_splits: int | None = None) -> torch.Tensor:
+    """q: [B, Tq, Hq, D] new-token queries (post-RoPE); kcache/vcache:
+    [B, Tmax, Hkv, D] with the new tokens' K/V already appended; lens, qlens:
+    [B] int32 on q's device. With n = clamp(lens[b], 0, Tmax) and
+    m = clamp(qlens[b], 0, min(Tq, n)), query i < m sits at position
+    n - m + i and attends to cache rows [0, n - m + i]; rows i >= m are zero
+    and their q contents do not matter. The host never reads lens or qlens,
+    so the call can be captured and a replay follows new contents. Returns
+    [B, Tq, Hq, D]."""
+    B, Tq, Hq, D = q.shape
+    Tmax, Hkv = kcache.shape[1], kcache.shape[2]
+    rep = max(1, Hq // max(1, Hkv))
+    if num_splits is None:
+        num_splits = extend_splits(B, Hkv, Tq, rep, Tmax)
+    if q.is_cuda:  # the binding refuses unsupported D and Hq/Hkv
+        return _require_ext("attention_extend").attn_extend(
+            q.contiguous(), kcache, vcache, lens, qlens, int(num_splits),
+            extend_chunk(Tmax, num_splits))
+    if D not in (64, 128):
+        raise ValueError(f"head_dim must be 64 or 128, got {D}")
+    if Hkv < 1 or Hq % Hkv or rep not in (1, 2, 4, 8):
+        raise ValueError(f"attention_extend: Hq/Hkv must be 1, 2, 4 or 8, "
+                         f"got {Hq}/{Hkv}")
+    n = lens.clamp(0, Tmax).view(B, 1)
+    m = torch.minimum(qlens.clamp(0, Tq).view(B, 1), n)
+    i = torch.arange(Tq).view(1, Tq)
+    limit = torch.where(i < m, n - m + i, -1)                 # [B,Tq]
+    dead = torch.arange(Tmax).view(1, 1, Tmax) > limit.unsqueeze(-1)
+    none = (limit < 0).view(B, 1, Tq, 1)
+    # rows a sequence must not read may hold anything, NaN included
+    gone = (torch.arange(Tmax).view(1, Tmax) >= n).view(B, Tmax, 1, 1)
+    kf = kcache.float().masked_fill(gone, 0.0)
+    vf = vcache.float().masked_fill(gone, 0.0)
+    kf = kf.permute(0, 2, 1, 3).repeat_interleave(rep, 1)     # [B,Hq,T,D]
+    vf = vf.permute(0, 2, 1, 3).repeat_interleave(rep, 1)
+    qf = q.float().permute(0, 2, 1, 3).masked_fill(none, 0.0)  # [B,Hq,Tq,D]
+    s = torch.einsum("bhid,bhtd->bhit", qf, kf) / (D ** 0.5)
+    s = s.masked_fill(dead.unsqueeze(1), float("-inf"))
+    p = torch.softmax(s, dim=-1).masked_fill(none, 0.0)
+    o = torch.einsum("bhit,bhtd->bhid", p, vf)
+    return o.permute(0, 2, 1, 3).to(q.dtype)
+
+
+@torch.no_grad()
+def qkv_rope_append_chunk_(qkv: torch.Tensor, cos: torch.Tensor,
+                           sin: torch.Tensor, pos: torch.Tensor,
+                           qlens: torch.Tensor, kcache: torch.Tensor,
+                           vcache: torch.Tensor, Hq: int, Hkv: int,
+                           D: int) -> torch.Tensor:
+    """qkv: [B, Tq, (Hq+2Hkv)*D]; pos, qlens: [B] int32 on qkv's device;
+    cos/sin: [>= Tmax, D/2]. Token i of sequence b is rotated at pos[b] + i
+    and its roped k and v copy are written into cache[b, pos[b] + i] in
+    place. A token is live iff i < qlens[b] and 0 <= pos[b] + i < Tmax; a
+    dead token writes nothing and gets a zero q row. Returns q
+    [B, Tq, Hq, D]."""
+    if qkv.is_cuda:
+        return _require_ext("qkv_rope_append_chunk").qkv_rope_append_chunk_(
+            qkv.contiguous(), cos, sin, pos, qlens, kcache, vcache, Hq, Hkv, D)
+    B, Tq = qkv.shape[0], qkv.shape[1]
+    Tmax = kcache.shape[1]
+    if cos.shape[0] < Tmax or sin.shape[0] < Tmax:
+        raise ValueError(
+            f"rope table has {cos.shape[0]} rows, cache needs {Tmax}")
+    i = torch.arange(Tq).view(1, Tq)
+    at = pos.long().view(B, 1) + i                            # [B,Tq]
+    live = (i < qlens.view(B, 1)) & (at >= 0) & (at < Tmax)
+    p = at.clamp(0, Tmax - 1)
+    parts = qkv.view(B, Tq, Hq + 2 * Hkv, D).float()
+    cs = cos[p].view(B, Tq, 1, D // 2)
+    sn = sin[p].view(B, Tq, 1, D // 2)
+
+    def rot(x):
+        x1, x2 = x[..., : D // 2], x[..., D // 2:]
+        return torch.cat([x1 * cs - x2 * sn, x2 * cs + x1 * sn], dim=-1)
+
+    q = rot(parts[:, :, :Hq]).to(qkv.dtype)
+    q = q.masked_fill(~live.view(B, Tq, 1, 1), 0)
+    k = rot(parts[:, :, Hq:Hq + Hkv]).to(kcache.dtype)
+    v = parts[:, :, Hq + Hkv:].to(vcache.dtype)
+    bi, ti = torch.nonzero(live, as_tuple=True)
+    kcache[bi, p[bi, ti]] = k[bi, ti]
+    vcache[bi, p[bi, ti]] = v[bi, ti]
+    return q
+
+
+# --------------------------------------------------------------------------
 # Token sampling: temperature / top-k / top-p, one draw per row (no autograd)
 # --------------------------------------------------------------------------
 _PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
@@ -1237,5 +1355,7 @@ __all__ = [
     "grad_sumsq_blocks", "grad_sumsq_", "grad_norm_finalize_",
     "attention_decode_ragged", "qkv_rope_append_",
     "decode_ragged_splits", "decode_ragged_chunk",
+    "attention_extend", "qkv_rope_append_chunk_",
+    "extend_splits", "extend_chunk",
     "sample_tokens", "sample_uniform", "philox4x32_10",
 ]

@@ -94,6 +94,17 @@ hipError_t tok_qkv_rope_append(const void* qkv, void* q, void* kcache,
                                const float* sin_tab, const int* pos, int B,
                                int Tmax, int Hq, int Hkv, int D,
                                hipStream_t stream);
+hipError_t tok_attn_extend(const void* q, const void* k, const void* v,
+                           const int* lens, const int* qlens, void* out,
+                           float* ws, int B, int Tq, int Tmax, int Hq, int Hkv,
+                           int D, int num_splits, int chunk,
+                           hipStream_t stream);
+hipError_t tok_qkv_rope_append_chunk(const void* qkv, void* q, void* kcache,
+                                     void* vcache, const float* cos_tab,
+                                     const float* sin_tab, const int* pos,
+                                     const int* qlens, int B, int Tq, int Tmax,
+                                     int Hq, int Hkv, int D,
+                                     hipStream_t stream);
 int tok_sample_max_vocab();
 hipError_t tok_sample_tokens(const void* logits, long row_stride,
                              const float* temperature, const int* top_k,
@@ -604,6 +615,97 @@ at::Tensor qkv_rope_append_(at::Tensor qkv, at::Tensor cos_tab,
   return q;
 }
 
+// q: [B, Tq, Hq, D] new-token queries; kcache/vcache: [B, Tmax, Hkv, D] with
+// the new tokens already appended; lens, qlens: [B] int32 on the device, never
+// read by the host. num_splits and chunk come from ops.extend_splits /
+// ops.extend_chunk (shapes alone).
+at::Tensor attn_extend(at::Tensor q, at::Tensor kcache, at::Tensor vcache,
+                       at::Tensor lens, at::Tensor qlens, long num_splits,
+                       long chunk) {
+  CHECK_BF16_CUDA(q);
+  CHECK_BF16_CUDA(kcache);
+  CHECK_BF16_CUDA(vcache);
+  TORCH_CHECK(q.dim() == 4 && kcache.dim() == 4,
+              "q [B,Tq,Hq,D], cache [B,T,Hkv,D]");
+  const long B = q.size(0), Tq = q.size(1), Hq = q.size(2), D = q.size(3);
+  const long Tmax = kcache.size(1), Hkv = kcache.size(2);
+  TORCH_CHECK(kcache.sizes() == vcache.sizes() && kcache.size(0) == B &&
+                  kcache.size(3) == D, "cache shape mismatch");
+  TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
+  TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  const long R = Hq / Hkv;
+  TORCH_CHECK(R == 1 || R == 2 || R == 4 || R == 8,
+              "attn_extend: Hq/Hkv must be 1, 2, 4 or 8, got ", R);
+  for (const at::Tensor* t : {&lens, &qlens})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt &&
+                    t->is_contiguous() && t->numel() == B,
+                "lens and qlens must be contiguous int32 GPU tensors of B "
+                "elements");
+  TORCH_CHECK(Tmax >= 1 && Tmax * Hkv * D * 2 < (1L << 31),
+              "one sequence's cache must stay under 2 GiB");
+  const long MT = (Tq * R + 63) / 64;
+  TORCH_CHECK(B >= 1 && B <= 65535 && Tq >= 1 && B * Tq <= 65535 &&
+                  Hkv * MT < (1L << 31) && num_splits >= 1 &&
+                  num_splits <= 1024, "grid out of range");
+  TORCH_CHECK(chunk >= 64 && chunk % 64 == 0 && num_splits * chunk >= Tmax,
+              "chunk must be a multiple of 64 and num_splits * chunk must "
+              "cover Tmax");
+  auto out = at::empty_like(q);
+  at::Tensor ws;
+  float* wsp = nullptr;
+  if (num_splits > 1) {
+    ws = at::empty({B * Tq * Hq * num_splits * (D + 2)},
+                   q.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  TOK_HIP_OK(tok_attn_extend(
+      q.data_ptr(), kcache.data_ptr(), vcache.data_ptr(),
+      lens.data_ptr<int>(), qlens.data_ptr<int>(), out.data_ptr(), wsp,
+      (int)B, (int)Tq, (int)Tmax, (int)Hq, (int)Hkv, (int)D, (int)num_splits,
+      (int)chunk, current_stream()));
+  return out;
+}
+
+// qkv: [B, Tq, (Hq+2Hkv)*D]; pos, qlens: [B] int32 on the device. Token i of
+// sequence b goes to cache[b, pos[b] + i]; returns roped q [B, Tq, Hq, D].
+at::Tensor qkv_rope_append_chunk_(at::Tensor qkv, at::Tensor cos_tab,
+                                  at::Tensor sin_tab, at::Tensor pos,
+                                  at::Tensor qlens, at::Tensor kcache,
+                                  at::Tensor vcache, long Hq, long Hkv,
+                                  long D) {
+  CHECK_BF16_CUDA(qkv);
+  CHECK_BF16_CUDA(kcache);
+  CHECK_BF16_CUDA(vcache);
+  TORCH_CHECK(cos_tab.is_cuda() && cos_tab.scalar_type() == at::kFloat &&
+              cos_tab.is_contiguous());
+  TORCH_CHECK(sin_tab.is_cuda() && sin_tab.scalar_type() == at::kFloat &&
+              sin_tab.is_contiguous());
+  TORCH_CHECK(D % 16 == 0, "head dim must be a multiple of 16");
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == (Hq + 2 * Hkv) * D,
+              "packed qkv must be [B, Tq, (Hq+2Hkv)*D]");
+  const long B = qkv.size(0), Tq = qkv.size(1);
+  TORCH_CHECK(kcache.dim() == 4 && kcache.sizes() == vcache.sizes() &&
+                  kcache.size(0) == B && kcache.size(2) == Hkv &&
+                  kcache.size(3) == D, "cache shape mismatch");
+  const long Tmax = kcache.size(1);
+  for (const at::Tensor* t : {&pos, &qlens})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt &&
+                    t->is_contiguous() && t->numel() == B,
+                "pos and qlens must be contiguous int32 GPU tensors of B "
+                "elements");
+  TORCH_CHECK(sin_tab.numel() == cos_tab.numel(), "cos/sin shape mismatch");
+  const long table_rows = cos_tab.numel() / (D / 2);
+  TORCH_CHECK(table_rows >= Tmax, "rope table has ", table_rows,
+              " rows, cache needs ", Tmax);
+  auto q = at::empty({B, Tq, Hq, D}, qkv.options());
+  TOK_HIP_OK(tok_qkv_rope_append_chunk(
+      qkv.data_ptr(), q.data_ptr(), kcache.data_ptr(), vcache.data_ptr(),
+      cos_tab.data_ptr<float>(), sin_tab.data_ptr<float>(),
+      pos.data_ptr<int>(), qlens.data_ptr<int>(), (int)B, (int)Tq, (int)Tmax,
+      (int)Hq, (int)Hkv, (int)D, current_stream()));
+  return q;
+}
+
 // logits: [B, V] bf16, unit stride in V, any row stride. The per-row
 // parameters are [B] device tensors that the host never reads; u replaces
 // the generator's draw when given. Returns int64 [B].
@@ -896,6 +998,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("num_splits"), py::arg("chunk"));
   mod.def("qkv_rope_append_", &qkv_rope_append_,
           "One-token packed-QKV RoPE + KV-cache append (bf16, gfx950)");
+  mod.def("attn_extend", &attn_extend,
+          "Multi-token attention over a ragged KV cache (bf16, gfx950)",
+          py::arg("q"), py::arg("kcache"), py::arg("vcache"), py::arg("lens"),
+          py::arg("qlens"), py::arg("num_splits"), py::arg("chunk"));
+  mod.def("qkv_rope_append_chunk_", &qkv_rope_append_chunk_,
+          "Multi-token packed-QKV RoPE + KV-cache append (bf16, gfx950)");
   mod.def("sample_tokens", &sample_tokens,
           "Fused temperature / top-k / top-p sampler (bf16, gfx950)",
           py::arg("logits"), py::arg("temperature"), py::arg("top_k"),

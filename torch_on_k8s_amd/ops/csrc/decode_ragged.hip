@@ -401,6 +401,16 @@ hipError_t tok_attn_decode_ragged(const void* q, const void* k, const void* v,
   return hipSuccess;
 }
 
+// The combine alone, for other producers of the same workspace layout
+// (attn_extend.hip): `rows` = product of the leading dims of out [rows,Hq,D].
+hipError_t tok_attn_ragged_combine(const float* ws, void* out, int rows,
+                                   int Hq, int D, int num_splits,
+                                   hipStream_t stream) {
+  attn_decode_ragged_combine<<<dim3(Hq, rows), D, 0, stream>>>(
+      ws, (bf16_t*)out, num_splits, D);
+  return hipGetLastError();
+}
+
 hipError_t tok_qkv_rope_append(const void* qkv, void* q, void* kcache,
                                void* vcache, const float* cos_tab,
                                const float* sin_tab, const int* pos, int B,

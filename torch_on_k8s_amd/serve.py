@@ -114,12 +114,12 @@ class InferenceServer:
     def generate(self, prompt_ids, max_new_tokens: int = 32,
                  temperature: float = 0.0, ragged: bool = False,
                  eos_token_id=None, top_k: int = 0, top_p: float = 1.0,
-                 seed=None):
+                 seed=None, prefill_chunk=None):
         import torch
         if ragged:
             return self._generate_ragged(prompt_ids, max_new_tokens,
                                          eos_token_id, temperature, top_k,
-                                         top_p, seed)
+                                         top_p, seed, prefill_chunk)
         dev = next(self.model.parameters()).device
         inp = torch.tensor(prompt_ids, dtype=torch.long, device=dev)
         t0 = time.perf_counter()
@@ -139,11 +139,13 @@ class InferenceServer:
         }
 
     def _generate_ragged(self, prompt_ids, max_new_tokens, eos_token_id,
-                         temperature=0.0, top_k=0, top_p=1.0, seed=None):
+                         temperature=0.0, top_k=0, top_p=1.0, seed=None,
+                         prefill_chunk=None):
         """Prompts of different lengths in one batch. new_tokens is the
         true count: a sequence that emitted eos stops there. A sampled
         request (temperature > 0) without a seed gets one here, and the
-        response carries it: row b draws with seed + b."""
+        response carries it: row b draws with seed + b. prefill_chunk, when
+        given, prefills through the cache in chunks of that many tokens."""
         import torch
         sampled = temperature > 0
         if sampled and seed is None:
@@ -153,7 +155,9 @@ class InferenceServer:
             outs = self.model.generate_ragged(
                 prompt_ids, max_new_tokens=max_new_tokens,
                 eos_token_id=eos_token_id, temperature=temperature,
-                top_k=top_k, top_p=top_p, seed=seed)
+                top_k=top_k, top_p=top_p, seed=seed,
+                **({} if prefill_chunk is None
+                   else {"prefill_chunk": prefill_chunk}))
         dt = time.perf_counter() - t0
         output_ids = [o.tolist() for o in outs]
         new_ids = [o[len(p):] for o, p in zip(output_ids, prompt_ids)]
@@ -183,6 +187,7 @@ def build_app(srv: InferenceServer):
         top_k: int = 0
         top_p: float = 1.0
         seed: int | None = None
+        prefill_chunk: int | None = Field(default=None, ge=1)
 
     app = FastAPI(title="torch-on-k8s-amd serving")
 
@@ -232,7 +237,8 @@ def build_app(srv: InferenceServer):
                                 temperature=req.temperature, ragged=True,
                                 eos_token_id=req.eos_token_id,
                                 top_k=req.top_k, top_p=req.top_p,
-                                seed=req.seed)
+                                seed=req.seed,
+                                prefill_chunk=req.prefill_chunk)
         except NotImplementedError as e:
             raise HTTPException(400, str(e))
 
@@ -252,6 +258,8 @@ def build_app(srv: InferenceServer):
         if req.top_k != 0 or req.top_p != 1.0 or req.seed is not None:
             raise HTTPException(400, 'sampling controls (top_k, top_p, seed) '
                                      'need "ragged": true')
+        if req.prefill_chunk is not None:
+            raise HTTPException(400, 'prefill_chunk needs "ragged": true')
         if len({len(p) for p in req.prompt_ids}) != 1:
             raise HTTPException(400, "all prompts must share one length")
         if vocab and any(t < 0 or t >= vocab
