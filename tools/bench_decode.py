@@ -24,6 +24,15 @@ Model level (llama-1b, B=8, 128-token prompts, 128 new tokens, graph on):
 ``generate_ragged`` at prompt lengths 16..128, and sampling: captured
 ``generate_ragged`` sampled (T=0.8, top-k 50, top-p 0.95) against the eager
 ``generate(temperature=0.8)``.
+
+``--kv-dtype fp8`` runs the FP8 KV-cache arm instead: the e4m3 decode kernel
+against the unchanged bf16 kernel at the same shapes and the default split
+count, equal and ragged lengths, in one process and interleaved rounds; ms
+and TB/s of the bytes actually read (bf16 rows, or codes plus row scales);
+the time ratio next to the byte ratio (D+4)/(2D). "faster" is printed for a
+shape only where the fp8 arm's slowest round beats the bf16 arm's fastest.
+Then llama-1b ``generate_ragged`` with and without ``kv_dtype="fp8"``: tok/s,
+the share of greedy tokens the two agree on, and the cache bytes per token.
 """
 import argparse
 import os
@@ -136,6 +145,145 @@ def kernel_level(args, ops, dev):
                       flush=True)
             del kc, vc
             torch.cuda.empty_cache()
+
+
+def fmt_ms(ts):
+    return (f"{statistics.median(ts) * 1e3:8.4f} "
+            f"[{min(ts) * 1e3:8.4f}..{max(ts) * 1e3:8.4f}] ms")
+
+
+def fp8_caches(nbuf, B, T, Hkv, D, dev, g):
+    """nbuf random e4m3 caches (no NaN codes) and their row scales."""
+    codes = torch.randint(0, 256, (2, nbuf, B, T, Hkv, D), device=dev,
+                          dtype=torch.uint8, generator=g)
+    codes[(codes & 0x7F) == 0x7F] = 0x3A
+    k8, v8 = (c.view(torch.float8_e4m3fn) for c in codes)
+    ks = (0.5 + torch.rand(nbuf, B, T, Hkv, device=dev, generator=g)) / 96
+    vs = (0.5 + torch.rand(nbuf, B, T, Hkv, device=dev, generator=g)) / 96
+    return k8, v8, ks, vs
+
+
+def time_interleaved(fns, nbuf, iters, rounds):
+    """Per-call seconds of each fn, `rounds` figures each: every fn warmed
+    and captured, then the graphs replayed alternately."""
+    for fn in fns:
+        for i in range(min(nbuf, 3)):
+            fn(i)
+    torch.cuda.synchronize()
+    graphs = [capture_calls(fn, nbuf, iters) for fn in fns]
+    for gr in graphs:
+        gr.replay()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(rounds):
+        for j, gr in enumerate(graphs):
+            times[j].append(time_graph(gr, iters))
+    return times
+
+
+def kernel_level_fp8(args, ops, dev):
+    Hq, Hkv, D = args.Hq, args.Hkv, args.D
+    byte_ratio = (D + 4) / (2 * D)
+    print(f"# fp8 KV cache, kernel level: Hq={Hq} Hkv={Hkv} D={D}, default "
+          f"splits, ms per call as median [min..max] over {args.rounds} "
+          f"interleaved rounds; TB/s = bytes of the valid rows actually read "
+          f"/ median; byte ratio fp8/bf16 = {byte_ratio:.3f}; copy ceiling "
+          f"{COPY_CEILING_TBS} TB/s")
+    for B in args.B:
+        for T in args.T:
+            rb16 = Hkv * D * 2 * 2                  # K + V rows, bf16
+            rb8 = Hkv * (D + 4) * 2                 # K + V codes + scales
+            nb16 = max(1, min(MAX_BUFS, -(-ROTATE_BYTES // (B * T * rb16))))
+            nb8 = max(1, min(MAX_BUFS, -(-ROTATE_BYTES // (B * T * rb8))))
+            g = torch.Generator(device=dev).manual_seed(0)
+            q = torch.randn(B, Hq, D, dtype=torch.bfloat16, device=dev,
+                            generator=g)
+            kc = torch.randn(nb16, B, T, Hkv, D, dtype=torch.bfloat16,
+                             device=dev, generator=g)
+            vc = torch.randn(nb16, B, T, Hkv, D, dtype=torch.bfloat16,
+                             device=dev, generator=g)
+            k8, v8, ks, vs = fp8_caches(nb8, B, T, Hkv, D, dev, g)
+            eq = torch.full((B,), T, dtype=torch.int32, device=dev)
+            rg = torch.randint(T // 8, T + 1, (B,),
+                               generator=torch.Generator().manual_seed(B + T)
+                               ).to(dev, torch.int32)
+            S = ops.decode_ragged_splits(B, Hkv, T)
+            est = max(20e-6, B * T * rb16 * 4 / 3e12)
+            iters = int(max(10, min(400, 25e-3 / est)))
+
+            def bf16(lens):
+                return lambda i: ops.attention_decode_ragged(
+                    q, kc[i % nb16], vc[i % nb16], lens)
+
+            def fp8(lens):
+                return lambda i: ops.attention_decode_ragged(
+                    q, k8[i % nb8], v8[i % nb8], lens, kscale=ks[i % nb8],
+                    vscale=vs[i % nb8])
+
+            cfgs = [("bf16 equal", bf16(eq), eq, rb16),
+                    ("fp8  equal", fp8(eq), eq, rb8),
+                    ("bf16 ragged", bf16(rg), rg, rb16),
+                    ("fp8  ragged", fp8(rg), rg, rb8)]
+            times = time_interleaved([c[1] for c in cfgs], max(nb16, nb8),
+                                     iters, args.rounds)
+            print(f"\nB={B} T={T} splits={S} caches bf16={nb16} fp8={nb8} "
+                  f"iters={iters} ragged_lens={int(rg.min())}..{int(rg.max())}"
+                  f" (sum {int(rg.sum())})")
+            for (name, _, lens, rb), ts in zip(cfgs, times):
+                tbs = int(lens.sum()) * rb / statistics.median(ts) / 1e12
+                print(f"  {name:12s} {fmt_ms(ts)}  {tbs:6.3f} TB/s",
+                      flush=True)
+            for j, kind in ((0, "equal"), (2, "ragged")):
+                t16, t8 = times[j], times[j + 1]
+                ratio = statistics.median(t8) / statistics.median(t16)
+                verdict = ("faster" if max(t8) < min(t16) else
+                           "slower" if min(t8) > max(t16) else "no claim")
+                print(f"  {kind:6s} time ratio fp8/bf16 = {ratio:.3f} (bytes "
+                      f"{byte_ratio:.3f}): {verdict}", flush=True)
+            del kc, vc, k8, v8, ks, vs
+            torch.cuda.empty_cache()
+
+
+def model_level_fp8(args, ops, dev):
+    from torch_on_k8s_amd.models.llama import LlamaModel, get_config
+    torch.manual_seed(0)
+    cfg = get_config(args.model)
+    model = LlamaModel(cfg).bfloat16().to(dev).eval()
+    B, S0, N = args.model_B, args.prompt_len, args.new_tokens
+    g = torch.Generator().manual_seed(1)
+    ids = torch.randint(0, cfg.vocab_size, (B, S0), generator=g).to(dev)
+    prompts = [ids[b] for b in range(B)]
+    runs = [("generate_ragged bf16 cache", lambda: model.generate_ragged(
+                prompts, max_new_tokens=N, use_graph=True)),
+            ("generate_ragged fp8 cache", lambda: model.generate_ragged(
+                prompts, max_new_tokens=N, use_graph=True, kv_dtype="fp8"))]
+    outs = [fn() for _, fn in runs]                         # warm
+    torch.cuda.synchronize()
+    times = [[] for _ in runs]
+    for _ in range(args.rounds):
+        for j, (_, fn) in enumerate(runs):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[j].append(time.perf_counter() - t0)
+    print(f"\n# fp8 KV cache, model level: {args.model} B={B} prompt={S0} "
+          f"new={N} graph on; whole call, {args.rounds} interleaved rounds, "
+          f"tok/s = B*new / wall")
+    for (name, _), ts in zip(runs, times):
+        rate = [B * N / t for t in ts]
+        print(f"  {name:28s} {statistics.median(rate):8.0f} tok/s "
+              f"[{min(rate):8.0f}..{max(rate):8.0f}]  "
+              f"{statistics.median(ts) * 1e3:7.1f} ms", flush=True)
+    same = sum(int((a[S0:] == b[S0:]).sum()) for a, b in zip(*outs))
+    print(f"  greedy tokens equal, fp8 vs bf16 cache: {same}/{B * N} "
+          f"({same / (B * N):.3f}; random weights, no threshold)")
+    for name, Hkv, D, L in ((args.model, cfg.num_kv_heads, cfg.head_dim,
+                             cfg.num_layers), ("Llama-8B shapes", 8, 128, 32)):
+        b16 = ops.kv_cache_bytes_per_token(Hkv, D, L)
+        b8 = ops.kv_cache_bytes_per_token(Hkv, D, L, "fp8")
+        print(f"  cache bytes per token, {name}: bf16 {b16}  fp8 {b8}  "
+              f"({b8 / b16:.3f})")
 
 
 SAMPLER_VOCABS = (32000, 128256)
@@ -269,6 +417,8 @@ def main():
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--skip-sampler", action="store_true")
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--kv-dtype", choices=["fp8"], default=None,
+                    help="run the FP8 KV-cache arm instead of the tables above")
     args = ap.parse_args()
     if args.rounds < 3:
         ap.error("--rounds must be >= 3: a figure needs its spread")
@@ -276,6 +426,12 @@ def main():
         sys.exit("bench_decode needs a GPU: a CPU timing says nothing here")
     from torch_on_k8s_amd import ops
     dev = torch.device("cuda", 0)
+    if args.kv_dtype == "fp8":
+        if not args.skip_kernel:
+            kernel_level_fp8(args, ops, dev)
+        if not args.skip_model:
+            model_level_fp8(args, ops, dev)
+        return
     if not args.skip_kernel:
         kernel_level(args, ops, dev)
     if not args.skip_sampler:

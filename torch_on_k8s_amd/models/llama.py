@@ -380,7 +380,8 @@ class LlamaModel(nn.Module):
                         pad_token_id: int = 0, *,
                         temperature=0.0, top_k=0, top_p=1.0,
                         seed=None,
-                        prefill_chunk: int | None = None
+                        prefill_chunk: int | None = None,
+                        kv_dtype: str | None = None
                         ) -> list[torch.Tensor]:
         """Generation for prompts of different lengths (each a 1-D id
         tensor or a list of ids, length >= 1). Returns one 1-D tensor per
@@ -410,9 +411,24 @@ class LlamaModel(nn.Module):
         ops.attention_extend, with per-sequence positions and lengths on
         the device, so no pad key is ever written or read and the
         activations are [B, N] wide. None (the default) is the padded
-        prefill above."""
+        prefill above.
+
+        kv_dtype="fp8" keeps the KV cache as OCP e4m3 codes with one fp32
+        scale per (token, kv head) row: (D + 4) / (2 D) of the bf16 cache.
+        The padded prefill attends to its bf16 q/k/v as before and stores
+        them through ops.kv_quantize_append_ (pad rows are not written); the
+        decode step is ops.qkv_rope_append_fp8_ + the fp8
+        ops.attention_decode_ragged, also inside the captured step. None
+        (the default) is the bf16 cache. Not available with prefill_chunk."""
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1 or None")
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_dtype must be None or 'fp8', got "
+                             f"{kv_dtype!r}")
+        fp8 = kv_dtype == "fp8"
+        if fp8 and prefill_chunk is not None:
+            raise ValueError("kv_dtype='fp8' has no chunked prefill: "
+                             "attention_extend reads a bf16 cache")
         cfg = self.cfg
         dev = self.embed_tokens.weight.device
         dtype = self.embed_tokens.weight.dtype
@@ -469,10 +485,16 @@ class LlamaModel(nn.Module):
                                device=dev)
         for b, s in enumerate(seqs):
             input_ids[b, :s.numel()] = s
-        kc = [torch.zeros(B, Tmax, Hkv, D, dtype=dtype, device=dev)
+        cache_dtype = torch.float8_e4m3fn if fp8 else dtype
+        kc = [torch.zeros(B, Tmax, Hkv, D, dtype=cache_dtype, device=dev)
               for _ in self.layers]
-        vc = [torch.zeros(B, Tmax, Hkv, D, dtype=dtype, device=dev)
+        vc = [torch.zeros(B, Tmax, Hkv, D, dtype=cache_dtype, device=dev)
               for _ in self.layers]
+        if fp8:
+            ks = [torch.zeros(B, Tmax, Hkv, device=dev) for _ in self.layers]
+            vs = [torch.zeros(B, Tmax, Hkv, device=dev) for _ in self.layers]
+            zero32 = torch.zeros(B, dtype=torch.int32, device=dev)
+            one32 = torch.ones(B, dtype=torch.int32, device=dev)
         cos, sin = build_rope_table(cfg, Tmax, dev)
 
         if prefill_chunk is None:
@@ -481,8 +503,13 @@ class LlamaModel(nn.Module):
             cs0, sn0 = cos[:S0].contiguous(), sin[:S0].contiguous()
             for i, blk in enumerate(self.layers):
                 q, k, v = blk.attn.project_qkv(blk.input_norm(x), cs0, sn0)
-                kc[i][:, :S0] = k
-                vc[i][:, :S0] = v
+                if fp8:
+                    ops.kv_quantize_append_(k, v, zero32,
+                                            lens0.to(torch.int32), kc[i],
+                                            vc[i], ks[i], vs[i])
+                else:
+                    kc[i][:, :S0] = k
+                    vc[i][:, :S0] = v
                 o = ops.attention(q, k, v, causal=True)
                 x = x + blk.attn.o_proj(o.reshape(B, S0, Hq * D))
                 x = x + blk.mlp(blk.post_attn_norm(x))
@@ -531,10 +558,18 @@ class LlamaModel(nn.Module):
             x = self.embed_tokens(token_buf)
             for i, blk in enumerate(self.layers):
                 h = blk.input_norm(x)
-                qkv = blk.attn.qkv_proj(h).view(B, (Hq + 2 * Hkv) * D)
-                q = ops.qkv_rope_append_(qkv, cos, sin, pos, kc[i], vc[i],
-                                         Hq, Hkv, D)
-                o = ops.attention_decode_ragged(q, kc[i], vc[i], lens)
+                qkv = blk.attn.qkv_proj(h)
+                if fp8:
+                    q = ops.qkv_rope_append_fp8_(
+                        qkv, cos, sin, pos, one32, kc[i], vc[i], ks[i],
+                        vs[i], Hq, Hkv, D).view(B, Hq, D)
+                    o = ops.attention_decode_ragged(
+                        q, kc[i], vc[i], lens, kscale=ks[i], vscale=vs[i])
+                else:
+                    q = ops.qkv_rope_append_(
+                        qkv.view(B, (Hq + 2 * Hkv) * D), cos, sin, pos,
+                        kc[i], vc[i], Hq, Hkv, D)
+                    o = ops.attention_decode_ragged(q, kc[i], vc[i], lens)
                 x = x + blk.attn.o_proj(o.view(B, 1, Hq * D))
                 x = x + blk.mlp(blk.post_attn_norm(x))
             nxt = pick(self.lm_head(self.norm(x))[:, -1], lens)

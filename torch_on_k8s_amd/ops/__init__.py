@@ -619,16 +619,32 @@ def decode_ragged_chunk(Tmax: int, num_splits: int) -> int:
 @torch.no_grad()
 def attention_decode_ragged(q: torch.Tensor, kcache: torch.Tensor,
                             vcache: torch.Tensor, lens: torch.Tensor, *,
+                            kscale: torch.Tensor | None = None,
+                            vscale: torch.Tensor | None = None,
                             num_splits: int | None = None) -> torch.Tensor:
     """q: [B, Hq, D] new-token queries (post-RoPE); kcache/vcache:
     [B, Tmax, Hkv, D]; lens: [B] int32 on q's device. Sequence b attends to
     rows [0, clamp(lens[b], 0, Tmax)); lens[b] == 0 gives a zero row. The
     host never reads lens, so the call can be captured and a replay follows
-    new contents. Returns [B, Hq, D]."""
+    new contents. Returns [B, Hq, D].
+
+    A torch.float8_e4m3fn cache needs kscale/vscale [B, Tmax, Hkv] fp32 (one
+    scale per (token, kv head) row, an element means float(code) * scale)
+    and runs attn_decode_ragged_fp8_kernel; a bf16 cache takes no scales."""
     B, Hq, D = q.shape
     Tmax, Hkv = kcache.shape[1], kcache.shape[2]
+    fp8 = kcache.dtype == torch.float8_e4m3fn
+    if fp8 and (kscale is None or vscale is None):
+        raise ValueError("an fp8 KV cache needs kscale and vscale")
+    if not fp8 and (kscale is not None or vscale is not None):
+        raise ValueError(f"kscale/vscale go with a float8_e4m3fn cache, got "
+                         f"{kcache.dtype}")
     if num_splits is None:
         num_splits = decode_ragged_splits(B, Hkv, Tmax)
+    if q.is_cuda and fp8:
+        return _require_ext("attention_decode_ragged").attn_decode_ragged_fp8(
+            q.contiguous(), kcache, vcache, kscale, vscale, lens,
+            int(num_splits), decode_ragged_chunk(Tmax, num_splits))
     if q.is_cuda:
         return _require_ext("attention_decode_ragged").attn_decode_ragged(
             q.contiguous(), kcache, vcache, lens, int(num_splits),
@@ -638,8 +654,11 @@ def attention_decode_ragged(q: torch.Tensor, kcache: torch.Tensor,
     dead = torch.arange(Tmax).view(1, 1, Tmax) >= n          # [B,1,Tmax]
     # rows a sequence must not read may hold anything, NaN included
     gone = dead.view(B, Tmax, 1, 1)
-    kf = kcache.float().masked_fill(gone, 0.0)
-    vf = vcache.float().masked_fill(gone, 0.0)
+    kf, vf = kcache.float(), vcache.float()
+    if fp8:
+        kf, vf = kf * kscale.unsqueeze(-1), vf * vscale.unsqueeze(-1)
+    kf = kf.masked_fill(gone, 0.0)
+    vf = vf.masked_fill(gone, 0.0)
     kf = kf.permute(0, 2, 1, 3).repeat_interleave(rep, 1)
     vf = vf.permute(0, 2, 1, 3).repeat_interleave(rep, 1)
     s = torch.einsum("bhd,bhtd->bht", q.float(), kf) / (D ** 0.5)
@@ -801,6 +820,117 @@ def qkv_rope_append_chunk_(qkv: torch.Tensor, cos: torch.Tensor,
     bi, ti = torch.nonzero(live, as_tuple=True)
     kcache[bi, p[bi, ti]] = k[bi, ti]
     vcache[bi, p[bi, ti]] = v[bi, ti]
+    return q
+
+
+# --------------------------------------------------------------------------
+# FP8 (OCP e4m3) KV cache: codes [B,Tmax,Hkv,D] + one fp32 scale per row
+# --------------------------------------------------------------------------
+FP8_MAX = 448.0
+
+
+def kv_cache_bytes_per_token(Hkv: int, D: int, layers: int,
+                             kv_dtype: str | None = None) -> int:
+    """K + V bytes one token occupies over all layers: bf16, or e4m3 codes
+    plus the fp32 row scales."""
+    per_row = D + 4 if kv_dtype == "fp8" else 2 * D
+    return 2 * layers * Hkv * per_row
+
+
+def quantize_rows_fp8(x: torch.Tensor):
+    """The cache format's quantizer on bf16 head rows x [..., D]: returns
+    (codes float8_e4m3fn [..., D], scale fp32 [...]). amax == 0 gives scale 0
+    and codes 0; otherwise scale = amax / 448 and a code is x * (1 / scale),
+    clamped to +-448 in fp32, rounded to nearest even."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    live = amax > 0
+    scale = torch.where(live, amax / FP8_MAX, torch.zeros_like(amax))
+    inv = torch.where(live, 1.0 / scale, torch.zeros_like(amax))
+    y = (xf * inv.unsqueeze(-1)).clamp(-FP8_MAX, FP8_MAX)
+    y = torch.where(live.unsqueeze(-1), y, torch.zeros_like(y))
+    return y.to(torch.float8_e4m3fn), scale
+
+
+def _check_fp8_cache(kcache, vcache, kscale, vscale, B, Hkv, D):
+    for t in (kcache, vcache):
+        if t.dtype != torch.float8_e4m3fn or t.dim() != 4:
+            raise ValueError("fp8 caches must be float8_e4m3fn [B,T,Hkv,D]")
+    if (kcache.shape != vcache.shape or kcache.shape[0] != B or
+            kcache.shape[2] != Hkv or kcache.shape[3] != D):
+        raise ValueError("cache shape mismatch")
+    for t in (kscale, vscale):
+        if t.dtype != torch.float32 or tuple(t.shape) != tuple(kcache.shape[:3]):
+            raise ValueError("kscale and vscale must be fp32 [B,T,Hkv]")
+
+
+def _fp8_store(cache, scale, codes, sc, bi, pi):
+    """cache[bi, pi] = codes, scale[bi, pi] = sc (index_put on the bytes)."""
+    cache.view(torch.uint8)[bi, pi] = codes.view(torch.uint8)
+    scale[bi, pi] = sc
+
+
+@torch.no_grad()
+def kv_quantize_append_(k: torch.Tensor, v: torch.Tensor, pos: torch.Tensor,
+                        qlens: torch.Tensor, kcache: torch.Tensor,
+                        vcache: torch.Tensor, kscale: torch.Tensor,
+                        vscale: torch.Tensor) -> None:
+    """k, v: [B, Tq, Hkv, D] bf16 (k already roped); pos, qlens: [B] int32 on
+    k's device. Token i of sequence b is quantized (quantize_rows_fp8) into
+    kcache/vcache[b, pos[b] + i] and kscale/vscale[b, pos[b] + i], in place.
+    A token is live iff i < qlens[b] and 0 <= pos[b] + i < Tmax; a dead token
+    writes neither codes nor scales."""
+    if k.is_cuda:
+        _require_ext("kv_quantize_append").kv_quantize_append_(
+            k.contiguous(), v.contiguous(), pos, qlens, kcache, vcache,
+            kscale, vscale)
+        return
+    if k.dim() != 4 or k.shape != v.shape:
+        raise ValueError("k and v must be [B, Tq, Hkv, D]")
+    B, Tq, Hkv, D = k.shape
+    _check_fp8_cache(kcache, vcache, kscale, vscale, B, Hkv, D)
+    Tmax = kcache.shape[1]
+    i = torch.arange(Tq).view(1, Tq)
+    at = pos.long().view(B, 1) + i
+    live = (i < qlens.view(B, 1)) & (at >= 0) & (at < Tmax)
+    bi, ti = torch.nonzero(live, as_tuple=True)
+    pi = at[bi, ti]
+    for x, cache, scale in ((k, kcache, kscale), (v, vcache, vscale)):
+        codes, sc = quantize_rows_fp8(x.to(torch.bfloat16))
+        _fp8_store(cache, scale, codes[bi, ti], sc[bi, ti], bi, pi)
+
+
+@torch.no_grad()
+def qkv_rope_append_fp8_(qkv: torch.Tensor, cos: torch.Tensor,
+                         sin: torch.Tensor, pos: torch.Tensor,
+                         qlens: torch.Tensor, kcache: torch.Tensor,
+                         vcache: torch.Tensor, kscale: torch.Tensor,
+                         vscale: torch.Tensor, Hq: int, Hkv: int,
+                         D: int) -> torch.Tensor:
+    """qkv_rope_append_chunk_ for an e4m3 cache: qkv [B, Tq, (Hq+2Hkv)*D];
+    token i of sequence b is rotated at pos[b] + i, and the bf16 k and v rows
+    the bf16 op would have stored are quantized (quantize_rows_fp8) into
+    cache[b, pos[b] + i] instead. Tq = 1 is the decode step. Returns bf16 q
+    [B, Tq, Hq, D], a zero row for a dead token."""
+    if qkv.is_cuda:
+        return _require_ext("qkv_rope_append_fp8").qkv_rope_append_fp8_(
+            qkv.contiguous(), cos, sin, pos, qlens, kcache, vcache, kscale,
+            vscale, Hq, Hkv, D)
+    B, Tq = qkv.shape[0], qkv.shape[1]
+    _check_fp8_cache(kcache, vcache, kscale, vscale, B, Hkv, D)
+    Tmax = kcache.shape[1]
+    # the bf16 op on a bf16 cache gives the rows to quantize
+    kb = torch.zeros(B, Tmax, Hkv, D, dtype=torch.bfloat16)
+    vb = torch.zeros_like(kb)
+    q = qkv_rope_append_chunk_(qkv, cos, sin, pos, qlens, kb, vb, Hq, Hkv, D)
+    i = torch.arange(Tq).view(1, Tq)
+    at = pos.long().view(B, 1) + i
+    live = (i < qlens.view(B, 1)) & (at >= 0) & (at < Tmax)
+    bi, ti = torch.nonzero(live, as_tuple=True)
+    pi = at[bi, ti]
+    for rows, cache, scale in ((kb, kcache, kscale), (vb, vcache, vscale)):
+        codes, sc = quantize_rows_fp8(rows[bi, pi])
+        _fp8_store(cache, scale, codes, sc, bi, pi)
     return q
 
 

@@ -105,6 +105,23 @@ hipError_t tok_qkv_rope_append_chunk(const void* qkv, void* q, void* kcache,
                                      const int* qlens, int B, int Tq, int Tmax,
                                      int Hq, int Hkv, int D,
                                      hipStream_t stream);
+hipError_t tok_attn_decode_ragged_fp8(const void* q, const void* k,
+                                      const void* v, const float* kscale,
+                                      const float* vscale, const int* lens,
+                                      void* out, float* ws, int B, int Tmax,
+                                      int Hq, int Hkv, int D, int num_splits,
+                                      int chunk, hipStream_t stream);
+hipError_t tok_kv_quantize_append(const void* k, const void* v, void* kcache,
+                                  void* vcache, float* kscale, float* vscale,
+                                  const int* pos, const int* qlens, int B,
+                                  int Tq, int Tmax, int Hkv, int D,
+                                  hipStream_t stream);
+hipError_t tok_qkv_rope_append_fp8(const void* qkv, void* q, void* kcache,
+                                   void* vcache, float* kscale, float* vscale,
+                                   const float* cos_tab, const float* sin_tab,
+                                   const int* pos, const int* qlens, int B,
+                                   int Tq, int Tmax, int Hq, int Hkv, int D,
+                                   hipStream_t stream);
 int tok_sample_max_vocab();
 hipError_t tok_sample_tokens(const void* logits, long row_stride,
                              const float* temperature, const int* top_k,
@@ -706,6 +723,131 @@ at::Tensor qkv_rope_append_chunk_(at::Tensor qkv, at::Tensor cos_tab,
   return q;
 }
 
+// An e4m3 KV cache [B,Tmax,Hkv,D] and its fp32 row scales [B,Tmax,Hkv].
+void check_fp8_cache(const at::Tensor& kcache, const at::Tensor& vcache,
+                     const at::Tensor& kscale, const at::Tensor& vscale,
+                     long B, long Hkv, long D) {
+  for (const at::Tensor* t : {&kcache, &vcache})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat8_e4m3fn &&
+                    t->is_contiguous() && t->dim() == 4,
+                "fp8 caches must be contiguous float8_e4m3fn GPU tensors "
+                "[B,T,Hkv,D]");
+  TORCH_CHECK(kcache.sizes() == vcache.sizes() && kcache.size(0) == B &&
+                  kcache.size(2) == Hkv && kcache.size(3) == D,
+              "cache shape mismatch");
+  for (const at::Tensor* t : {&kscale, &vscale})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat &&
+                    t->is_contiguous() && t->dim() == 3 &&
+                    t->size(0) == B && t->size(1) == kcache.size(1) &&
+                    t->size(2) == Hkv,
+                "kscale and vscale must be contiguous fp32 GPU tensors "
+                "[B,T,Hkv]");
+  TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
+}
+
+// attn_decode_ragged over an e4m3 cache with one fp32 scale per (token, kv
+// head) row.
+at::Tensor attn_decode_ragged_fp8(at::Tensor q, at::Tensor kcache,
+                                  at::Tensor vcache, at::Tensor kscale,
+                                  at::Tensor vscale, at::Tensor lens,
+                                  long num_splits, long chunk) {
+  CHECK_BF16_CUDA(q);
+  TORCH_CHECK(q.dim() == 3 && kcache.dim() == 4, "q [B,Hq,D], cache [B,T,Hkv,D]");
+  const long B = q.size(0), Hq = q.size(1), D = q.size(2);
+  const long Tmax = kcache.size(1), Hkv = kcache.size(2);
+  check_fp8_cache(kcache, vcache, kscale, vscale, B, Hkv, D);
+  TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  const long R = Hq / Hkv;
+  TORCH_CHECK(R == 1 || R == 2 || R == 4 || R == 8,
+              "attn_decode_ragged_fp8: Hq/Hkv must be 1, 2, 4 or 8, got ", R);
+  TORCH_CHECK(lens.is_cuda() && lens.scalar_type() == at::kInt &&
+                  lens.is_contiguous() && lens.numel() == B,
+              "lens must be a contiguous int32 GPU tensor of B elements");
+  TORCH_CHECK(Tmax >= 1 && Tmax < (1L << 26), "Tmax out of range");
+  TORCH_CHECK(B >= 1 && B <= 65535 && num_splits >= 1 && num_splits <= 1024,
+              "grid out of range");
+  TORCH_CHECK(chunk >= 1 && num_splits * chunk >= Tmax,
+              "num_splits * chunk must cover Tmax");
+  auto out = at::empty_like(q);
+  at::Tensor ws;
+  float* wsp = nullptr;
+  if (num_splits > 1) {
+    ws = at::empty({B * Hq * num_splits * (D + 2)},
+                   q.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  TOK_HIP_OK(tok_attn_decode_ragged_fp8(
+      q.data_ptr(), kcache.data_ptr(), vcache.data_ptr(),
+      kscale.data_ptr<float>(), vscale.data_ptr<float>(),
+      lens.data_ptr<int>(), out.data_ptr(), wsp, (int)B, (int)Tmax, (int)Hq,
+      (int)Hkv, (int)D, (int)num_splits, (int)chunk, current_stream()));
+  return out;
+}
+
+// k, v: [B, Tq, Hkv, D] bf16 (k already roped); pos, qlens: [B] int32 on the
+// device. Token i of sequence b is quantized into cache[b, pos[b] + i].
+void kv_quantize_append_(at::Tensor k, at::Tensor v, at::Tensor pos,
+                         at::Tensor qlens, at::Tensor kcache,
+                         at::Tensor vcache, at::Tensor kscale,
+                         at::Tensor vscale) {
+  CHECK_BF16_CUDA(k);
+  CHECK_BF16_CUDA(v);
+  TORCH_CHECK(k.dim() == 4 && k.sizes() == v.sizes(),
+              "k and v must be [B, Tq, Hkv, D]");
+  const long B = k.size(0), Tq = k.size(1), Hkv = k.size(2), D = k.size(3);
+  check_fp8_cache(kcache, vcache, kscale, vscale, B, Hkv, D);
+  for (const at::Tensor* t : {&pos, &qlens})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt &&
+                    t->is_contiguous() && t->numel() == B,
+                "pos and qlens must be contiguous int32 GPU tensors of B "
+                "elements");
+  TORCH_CHECK(B >= 1 && Tq >= 1 && B * Tq < (1L << 31), "B * Tq out of range");
+  TOK_HIP_OK(tok_kv_quantize_append(
+      k.data_ptr(), v.data_ptr(), kcache.data_ptr(), vcache.data_ptr(),
+      kscale.data_ptr<float>(), vscale.data_ptr<float>(),
+      pos.data_ptr<int>(), qlens.data_ptr<int>(), (int)B, (int)Tq,
+      (int)kcache.size(1), (int)Hkv, (int)D, current_stream()));
+}
+
+// qkv: [B, Tq, (Hq+2Hkv)*D]; pos, qlens: [B] int32 on the device. Token i of
+// sequence b is rotated at pos[b] + i and its k, v quantized into
+// cache[b, pos[b] + i]; returns roped bf16 q [B, Tq, Hq, D].
+at::Tensor qkv_rope_append_fp8_(at::Tensor qkv, at::Tensor cos_tab,
+                                at::Tensor sin_tab, at::Tensor pos,
+                                at::Tensor qlens, at::Tensor kcache,
+                                at::Tensor vcache, at::Tensor kscale,
+                                at::Tensor vscale, long Hq, long Hkv,
+                                long D) {
+  CHECK_BF16_CUDA(qkv);
+  TORCH_CHECK(cos_tab.is_cuda() && cos_tab.scalar_type() == at::kFloat &&
+              cos_tab.is_contiguous());
+  TORCH_CHECK(sin_tab.is_cuda() && sin_tab.scalar_type() == at::kFloat &&
+              sin_tab.is_contiguous());
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == (Hq + 2 * Hkv) * D,
+              "packed qkv must be [B, Tq, (Hq+2Hkv)*D]");
+  const long B = qkv.size(0), Tq = qkv.size(1);
+  check_fp8_cache(kcache, vcache, kscale, vscale, B, Hkv, D);
+  const long Tmax = kcache.size(1);
+  for (const at::Tensor* t : {&pos, &qlens})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt &&
+                    t->is_contiguous() && t->numel() == B,
+                "pos and qlens must be contiguous int32 GPU tensors of B "
+                "elements");
+  TORCH_CHECK(B >= 1 && Tq >= 1 && B * Tq < (1L << 31), "B * Tq out of range");
+  TORCH_CHECK(sin_tab.numel() == cos_tab.numel(), "cos/sin shape mismatch");
+  const long table_rows = cos_tab.numel() / (D / 2);
+  TORCH_CHECK(table_rows >= Tmax, "rope table has ", table_rows,
+              " rows, cache needs ", Tmax);
+  auto q = at::empty({B, Tq, Hq, D}, qkv.options());
+  TOK_HIP_OK(tok_qkv_rope_append_fp8(
+      qkv.data_ptr(), q.data_ptr(), kcache.data_ptr(), vcache.data_ptr(),
+      kscale.data_ptr<float>(), vscale.data_ptr<float>(),
+      cos_tab.data_ptr<float>(), sin_tab.data_ptr<float>(),
+      pos.data_ptr<int>(), qlens.data_ptr<int>(), (int)B, (int)Tq, (int)Tmax,
+      (int)Hq, (int)Hkv, (int)D, current_stream()));
+  return q;
+}
+
 // logits: [B, V] bf16, unit stride in V, any row stride. The per-row
 // parameters are [B] device tensors that the host never reads; u replaces
 // the generator's draw when given. Returns int64 [B].
@@ -1004,6 +1146,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("qlens"), py::arg("num_splits"), py::arg("chunk"));
   mod.def("qkv_rope_append_chunk_", &qkv_rope_append_chunk_,
           "Multi-token packed-QKV RoPE + KV-cache append (bf16, gfx950)");
+  mod.def("attn_decode_ragged_fp8", &attn_decode_ragged_fp8,
+          "Per-sequence-length decode over an e4m3 KV cache with per-row "
+          "scales (gfx950)",
+          py::arg("q"), py::arg("kcache"), py::arg("vcache"),
+          py::arg("kscale"), py::arg("vscale"), py::arg("lens"),
+          py::arg("num_splits"), py::arg("chunk"));
+  mod.def("kv_quantize_append_", &kv_quantize_append_,
+          "Quantize roped bf16 K/V rows into an e4m3 KV cache (gfx950)");
+  mod.def("qkv_rope_append_fp8_", &qkv_rope_append_fp8_,
+          "Multi-token packed-QKV RoPE + e4m3 KV-cache append (gfx950)");
   mod.def("sample_tokens", &sample_tokens,
           "Fused temperature / top-k / top-p sampler (bf16, gfx950)",
           py::arg("logits"), py::arg("temperature"), py::arg("top_k"),

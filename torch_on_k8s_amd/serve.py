@@ -27,7 +27,9 @@ Endpoints:
                                   at its first eos; "temperature", "top_k",
                                   "top_p" and "seed" sample inside the
                                   captured decode step, and the response
-                                  carries the "seed" that was used
+                                  carries the "seed" that was used;
+                                  "kv_dtype": "fp8" keeps the KV cache in
+                                  e4m3 with per-row scales (ragged only)
 
 Prompts are token IDs: this framework is tokenizer-free by design
 (synthetic-data training; no network for vocab downloads).
@@ -114,12 +116,12 @@ class InferenceServer:
     def generate(self, prompt_ids, max_new_tokens: int = 32,
                  temperature: float = 0.0, ragged: bool = False,
                  eos_token_id=None, top_k: int = 0, top_p: float = 1.0,
-                 seed=None, prefill_chunk=None):
+                 seed=None, prefill_chunk=None, kv_dtype=None):
         import torch
         if ragged:
             return self._generate_ragged(prompt_ids, max_new_tokens,
                                          eos_token_id, temperature, top_k,
-                                         top_p, seed, prefill_chunk)
+                                         top_p, seed, prefill_chunk, kv_dtype)
         dev = next(self.model.parameters()).device
         inp = torch.tensor(prompt_ids, dtype=torch.long, device=dev)
         t0 = time.perf_counter()
@@ -140,12 +142,13 @@ class InferenceServer:
 
     def _generate_ragged(self, prompt_ids, max_new_tokens, eos_token_id,
                          temperature=0.0, top_k=0, top_p=1.0, seed=None,
-                         prefill_chunk=None):
+                         prefill_chunk=None, kv_dtype=None):
         """Prompts of different lengths in one batch. new_tokens is the
         true count: a sequence that emitted eos stops there. A sampled
         request (temperature > 0) without a seed gets one here, and the
         response carries it: row b draws with seed + b. prefill_chunk, when
-        given, prefills through the cache in chunks of that many tokens."""
+        given, prefills through the cache in chunks of that many tokens;
+        kv_dtype="fp8" keeps the KV cache in e4m3 with per-row scales."""
         import torch
         sampled = temperature > 0
         if sampled and seed is None:
@@ -157,7 +160,8 @@ class InferenceServer:
                 eos_token_id=eos_token_id, temperature=temperature,
                 top_k=top_k, top_p=top_p, seed=seed,
                 **({} if prefill_chunk is None
-                   else {"prefill_chunk": prefill_chunk}))
+                   else {"prefill_chunk": prefill_chunk}),
+                **({} if kv_dtype is None else {"kv_dtype": kv_dtype}))
         dt = time.perf_counter() - t0
         output_ids = [o.tolist() for o in outs]
         new_ids = [o[len(p):] for o, p in zip(output_ids, prompt_ids)]
@@ -188,6 +192,7 @@ def build_app(srv: InferenceServer):
         top_p: float = 1.0
         seed: int | None = None
         prefill_chunk: int | None = Field(default=None, ge=1)
+        kv_dtype: str | None = None
 
     app = FastAPI(title="torch-on-k8s-amd serving")
 
@@ -232,13 +237,20 @@ def build_app(srv: InferenceServer):
                 400, f"prompt+max_new_tokens exceeds the model's trained "
                      f"context ({max_seq}); RoPE extrapolation beyond it "
                      f"degrades silently")
+        if req.kv_dtype not in (None, "fp8"):
+            raise HTTPException(400, 'kv_dtype must be "fp8" or absent')
+        if req.kv_dtype is not None and req.prefill_chunk is not None:
+            raise HTTPException(400, "kv_dtype and prefill_chunk do not "
+                                     "combine: chunked prefill reads a bf16 "
+                                     "cache")
         try:
             return srv.generate(req.prompt_ids, req.max_new_tokens,
                                 temperature=req.temperature, ragged=True,
                                 eos_token_id=req.eos_token_id,
                                 top_k=req.top_k, top_p=req.top_p,
                                 seed=req.seed,
-                                prefill_chunk=req.prefill_chunk)
+                                prefill_chunk=req.prefill_chunk,
+                                kv_dtype=req.kv_dtype)
         except NotImplementedError as e:
             raise HTTPException(400, str(e))
 
@@ -260,6 +272,8 @@ def build_app(srv: InferenceServer):
                                      'need "ragged": true')
         if req.prefill_chunk is not None:
             raise HTTPException(400, 'prefill_chunk needs "ragged": true')
+        if req.kv_dtype is not None:
+            raise HTTPException(400, 'kv_dtype needs "ragged": true')
         if len({len(p) for p in req.prompt_ids}) != 1:
             raise HTTPException(400, "all prompts must share one length")
         if vocab and any(t < 0 or t >= vocab
