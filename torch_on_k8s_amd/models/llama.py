@@ -381,7 +381,8 @@ class LlamaModel(nn.Module):
                         temperature=0.0, top_k=0, top_p=1.0,
                         seed=None,
                         prefill_chunk: int | None = None,
-                        kv_dtype: str | None = None
+                        kv_dtype: str | None = None,
+                        weight_dtype: str | None = None
                         ) -> list[torch.Tensor]:
         """Generation for prompts of different lengths (each a 1-D id
         tensor or a list of ids, length >= 1). Returns one 1-D tensor per
@@ -419,12 +420,28 @@ class LlamaModel(nn.Module):
         them through ops.kv_quantize_append_ (pad rows are not written); the
         decode step is ops.qkv_rope_append_fp8_ + the fp8
         ops.attention_decode_ragged, also inside the captured step. None
-        (the default) is the bf16 cache. Not available with prefill_chunk."""
+        (the default) is the bf16 cache. Not available with prefill_chunk.
+
+        weight_dtype="fp8" runs the five projections (qkv_proj, o_proj,
+        gate_up_proj, down_proj, lm_head) of the prefill and of the decode
+        step, eager and captured, through ops.linear_w8 on e4m3 weight codes
+        with one fp32 scale per output channel: a decode step reads half the
+        weight bytes. The codes are built on first use by
+        ops.quantize_weight_fp8 and kept on the model outside state_dict,
+        per weight and keyed by (data_ptr, _version), so a changed weight is
+        requantized; drop_quantized_weights() frees them. The bf16 weights
+        stay resident, and the embedding lookup stays bf16 also with
+        tie_embeddings. None (the default) is the bf16 path. Combines with
+        kv_dtype, prefill_chunk and the sampling arguments."""
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1 or None")
         if kv_dtype not in (None, "fp8"):
             raise ValueError(f"kv_dtype must be None or 'fp8', got "
                              f"{kv_dtype!r}")
+        if weight_dtype not in (None, "fp8"):
+            raise ValueError(f"weight_dtype must be None or 'fp8', got "
+                             f"{weight_dtype!r}")
+        w8 = weight_dtype == "fp8"
         fp8 = kv_dtype == "fp8"
         if fp8 and prefill_chunk is not None:
             raise ValueError("kv_dtype='fp8' has no chunked prefill: "
@@ -469,6 +486,19 @@ class LlamaModel(nn.Module):
                                   dtype=torch.float32, device=dev)
             seed_t = torch.tensor(seeds, dtype=torch.long, device=dev)
 
+        def lin(mod, x):
+            """A projection: the module's own call, or ops.linear_w8 over
+            its quantized weight."""
+            if not w8:
+                return mod(x)
+            return ops.linear_w8(x, *self._quantized(mod.weight))
+
+        def mlp(blk, x):
+            if not w8:
+                return blk.mlp(x)
+            return lin(blk.mlp.down_proj,
+                       ops.swiglu(lin(blk.mlp.gate_up_proj, x)))
+
         def pick(logits, index):
             """Next token per row of logits [B, V]; index [B] is where in
             its sequence each token will sit (the draw's counter)."""
@@ -502,7 +532,13 @@ class LlamaModel(nn.Module):
             x = self.embed_tokens(input_ids)
             cs0, sn0 = cos[:S0].contiguous(), sin[:S0].contiguous()
             for i, blk in enumerate(self.layers):
-                q, k, v = blk.attn.project_qkv(blk.input_norm(x), cs0, sn0)
+                if w8:
+                    q, k, v = ops.qkv_rope(
+                        lin(blk.attn.qkv_proj, blk.input_norm(x)), cs0, sn0,
+                        Hq, Hkv, D)
+                else:
+                    q, k, v = blk.attn.project_qkv(blk.input_norm(x), cs0,
+                                                   sn0)
                 if fp8:
                     ops.kv_quantize_append_(k, v, zero32,
                                             lens0.to(torch.int32), kc[i],
@@ -511,8 +547,8 @@ class LlamaModel(nn.Module):
                     kc[i][:, :S0] = k
                     vc[i][:, :S0] = v
                 o = ops.attention(q, k, v, causal=True)
-                x = x + blk.attn.o_proj(o.reshape(B, S0, Hq * D))
-                x = x + blk.mlp(blk.post_attn_norm(x))
+                x = x + lin(blk.attn.o_proj, o.reshape(B, S0, Hq * D))
+                x = x + mlp(blk, blk.post_attn_norm(x))
             last = x[torch.arange(B, device=dev), lens0 - 1].unsqueeze(1)
         else:
             # prefill through the cache, N tokens per sequence at a time
@@ -530,18 +566,19 @@ class LlamaModel(nn.Module):
                 clen = len32.clamp(max=c0 + N)
                 x = self.embed_tokens(ids)
                 for i, blk in enumerate(self.layers):
-                    qkv = blk.attn.qkv_proj(blk.input_norm(x))
+                    qkv = lin(blk.attn.qkv_proj, blk.input_norm(x))
                     q = ops.qkv_rope_append_chunk_(qkv, cos, sin, cpos, cql,
                                                    kc[i], vc[i], Hq, Hkv, D)
                     o = ops.attention_extend(q, kc[i], vc[i], clen, cql)
-                    x = x + blk.attn.o_proj(o.reshape(B, N, Hq * D))
-                    x = x + blk.mlp(blk.post_attn_norm(x))
+                    x = x + lin(blk.attn.o_proj, o.reshape(B, N, Hq * D))
+                    x = x + mlp(blk, blk.post_attn_norm(x))
                 # the chunk that holds a sequence's last prompt token
                 at = lens0 - 1 - c0
                 here = ((at >= 0) & (at < N)).view(B, 1, 1)
                 last = torch.where(here, x[rows, at.clamp(0, N - 1)]
                                    .unsqueeze(1), last)
-        first = pick(self.lm_head(self.norm(last))[:, -1], lens0).unsqueeze(1)
+        first = pick(lin(self.lm_head, self.norm(last))[:, -1],
+                     lens0).unsqueeze(1)
 
         # Decode state, all on the device. token_buf holds the token to
         # feed; it sits at position pos = lens - 1 and attends to lens rows.
@@ -558,7 +595,7 @@ class LlamaModel(nn.Module):
             x = self.embed_tokens(token_buf)
             for i, blk in enumerate(self.layers):
                 h = blk.input_norm(x)
-                qkv = blk.attn.qkv_proj(h)
+                qkv = lin(blk.attn.qkv_proj, h)
                 if fp8:
                     q = ops.qkv_rope_append_fp8_(
                         qkv, cos, sin, pos, one32, kc[i], vc[i], ks[i],
@@ -570,9 +607,9 @@ class LlamaModel(nn.Module):
                         qkv.view(B, (Hq + 2 * Hkv) * D), cos, sin, pos,
                         kc[i], vc[i], Hq, Hkv, D)
                     o = ops.attention_decode_ragged(q, kc[i], vc[i], lens)
-                x = x + blk.attn.o_proj(o.view(B, 1, Hq * D))
-                x = x + blk.mlp(blk.post_attn_norm(x))
-            nxt = pick(self.lm_head(self.norm(x))[:, -1], lens)
+                x = x + lin(blk.attn.o_proj, o.view(B, 1, Hq * D))
+                x = x + mlp(blk, blk.post_attn_norm(x))
+            nxt = pick(lin(self.lm_head, self.norm(x))[:, -1], lens)
             nxt = torch.where(finished, eos, nxt)
             finished.logical_or_(nxt == eos)
             token_buf.copy_(nxt.unsqueeze(1))  # self-feed the next replay
@@ -612,6 +649,21 @@ class LlamaModel(nn.Module):
             out.append(torch.cat([s, torch.tensor(row, dtype=torch.long,
                                                   device=dev)]))
         return out
+
+    def _quantized(self, weight: torch.Tensor):
+        """(codes, wscale) of a projection weight for weight_dtype="fp8",
+        built on first use and again after the weight changed."""
+        cache = self.__dict__.setdefault("_w8_cache", {})
+        key = weight.data_ptr()
+        ent = cache.get(key)
+        if ent is None or ent[0] != weight._version:
+            ent = (weight._version, *ops.quantize_weight_fp8(weight))
+            cache[key] = ent
+        return ent[1], ent[2]
+
+    def drop_quantized_weights(self) -> None:
+        """Free the e4m3 copies that weight_dtype="fp8" built."""
+        self.__dict__.pop("_w8_cache", None)
 
     def num_params(self) -> int:
         seen, total = set(), 0

@@ -935,6 +935,83 @@ def qkv_rope_append_fp8_(qkv: torch.Tensor, cos: torch.Tensor,
 
 
 # --------------------------------------------------------------------------
+# FP8 (OCP e4m3) weight-only linear: codes [N,K] + one fp32 scale per channel
+# --------------------------------------------------------------------------
+_W8_TARGET_BLOCKS = 512    # about two blocks per CU (256 CUs)
+_W8_BLOCK_N = 64           # output channels per block of linear_w8_kernel
+_W8_STEP_K = 128           # k per step
+_W8_MIN_STEPS = 4          # K-steps per split, at least
+_W8_MAX_SPLITS = 16
+_W8_MAX_M = 64             # rows the kernel serves; above it: dequant + GEMM
+
+
+def quantize_weight_fp8(w: torch.Tensor):
+    """A 2-D weight [N, K] as (codes float8_e4m3fn [N, K], wscale fp32 [N]):
+    quantize_rows_fp8 on its bf16 rows, one scale per output channel."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_weight_fp8 takes a 2-D weight, got "
+                         f"{tuple(w.shape)}")
+    return quantize_rows_fp8(w.detach().to(torch.bfloat16))
+
+
+def linear_w8_splits(M: int, N: int, K: int) -> int:
+    """Default K-split count of linear_w8. Depends on shapes alone, so a
+    captured grid stays valid: about two blocks per CU over the ceil(N/64)
+    channel blocks, never fewer than four 128-wide K-steps per split, at
+    most 16 splits. M does not enter: a block serves every row."""
+    blocks = -(-N // _W8_BLOCK_N)
+    want = _W8_TARGET_BLOCKS // max(1, blocks)
+    return max(1, min(want, (K // _W8_STEP_K) // _W8_MIN_STEPS,
+                      _W8_MAX_SPLITS))
+
+
+def _check_w8(x, codes, wscale):
+    if codes.dtype != torch.float8_e4m3fn or codes.dim() != 2:
+        raise ValueError("codes must be float8_e4m3fn [N,K]")
+    if wscale.dtype != torch.float32 or tuple(wscale.shape) != (codes.shape[0],):
+        raise ValueError("wscale must be fp32 [N]")
+    if x.shape[-1] != codes.shape[1]:
+        raise ValueError(f"x has {x.shape[-1]} features, codes have "
+                         f"K = {codes.shape[1]}")
+
+
+@torch.no_grad()
+def w8_dequant(codes: torch.Tensor, wscale: torch.Tensor) -> torch.Tensor:
+    """bf16(float(codes) * wscale[:, None]) as a [N, K] bf16 weight: one fp32
+    product and one rounding per element."""
+    if codes.is_cuda:
+        return _require_ext("w8_dequant").w8_dequant(codes, wscale)
+    return (codes.float() * wscale[:, None]).to(torch.bfloat16)
+
+
+@torch.no_grad()
+def linear_w8(x: torch.Tensor, codes: torch.Tensor, wscale: torch.Tensor, *,
+              num_splits: int | None = None) -> torch.Tensor:
+    """y = x @ (float(codes) * wscale[:, None])^T over the last dimension of
+    x. codes: [N, K] float8_e4m3fn in the nn.Linear layout, wscale: [N] fp32
+    (ops.quantize_weight_fp8). On the GPU x is bf16, K % 128 == 0 and
+    N % 16 == 0; up to 64 rows run linear_w8_kernel (the e4m3 codes are
+    widened in registers and fed to bf16 MFMAs, no rounding before the fp32
+    accumulator), more rows dequantize to a bf16 temporary and make the
+    library call of the bf16 path. No autograd: a serving op."""
+    _check_w8(x, codes, wscale)
+    N, K = codes.shape
+    if not x.is_cuda:
+        return torch.nn.functional.linear(
+            x.float(), codes.float() * wscale[:, None]).to(x.dtype)
+    x2 = x.reshape(-1, K).contiguous()
+    M = x2.shape[0]
+    ext = _require_ext("linear_w8")
+    if M <= _W8_MAX_M:
+        if num_splits is None:
+            num_splits = linear_w8_splits(M, N, K)
+        y = ext.linear_w8(x2, codes, wscale, int(num_splits))
+    else:
+        y = torch.nn.functional.linear(x2, ext.w8_dequant(codes, wscale))
+    return y.view(*x.shape[:-1], N)
+
+
+# --------------------------------------------------------------------------
 # Token sampling: temperature / top-k / top-p, one draw per row (no autograd)
 # --------------------------------------------------------------------------
 _PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
@@ -1488,4 +1565,5 @@ __all__ = [
     "attention_extend", "qkv_rope_append_chunk_",
     "extend_splits", "extend_chunk",
     "sample_tokens", "sample_uniform", "philox4x32_10",
+    "linear_w8", "linear_w8_splits", "quantize_weight_fp8", "w8_dequant",
 ]

@@ -122,6 +122,11 @@ hipError_t tok_qkv_rope_append_fp8(const void* qkv, void* q, void* kcache,
                                    const int* pos, const int* qlens, int B,
                                    int Tq, int Tmax, int Hq, int Hkv, int D,
                                    hipStream_t stream);
+hipError_t tok_linear_w8(const void* x, const void* code, const float* wscale,
+                         void* y, float* ws, int M, int N, int K,
+                         int num_splits, hipStream_t stream);
+hipError_t tok_w8_dequant(const void* code, const float* wscale, void* out,
+                          long N, int K, hipStream_t stream);
 int tok_sample_max_vocab();
 hipError_t tok_sample_tokens(const void* logits, long row_stride,
                              const float* temperature, const int* top_k,
@@ -848,6 +853,63 @@ at::Tensor qkv_rope_append_fp8_(at::Tensor qkv, at::Tensor cos_tab,
   return q;
 }
 
+// e4m3 weight codes [N,K] in the nn.Linear layout and one fp32 scale per
+// output channel.
+void check_w8_weight(const at::Tensor& codes, const at::Tensor& wscale) {
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kFloat8_e4m3fn &&
+                  codes.is_contiguous() && codes.dim() == 2,
+              "codes must be a contiguous float8_e4m3fn GPU tensor [N,K]");
+  TORCH_CHECK(wscale.is_cuda() && wscale.scalar_type() == at::kFloat &&
+                  wscale.is_contiguous() && wscale.dim() == 1 &&
+                  wscale.size(0) == codes.size(0),
+              "wscale must be a contiguous fp32 GPU tensor [N]");
+  const long N = codes.size(0), K = codes.size(1);
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && K < (1L << 22),
+              "linear_w8: K must be a multiple of 128 (below 2^22), got ", K);
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && N <= 64L * 65535,
+              "linear_w8: N must be a multiple of 16, got ", N);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(wscale.data_ptr()) % 4 == 0,
+              "linear_w8: codes must be 16-byte aligned");
+}
+
+// y[M,N] = x[M,K] . (float(codes[N,K]) * wscale[N])^T for 1 <= M <= 64.
+at::Tensor linear_w8(at::Tensor x, at::Tensor codes, at::Tensor wscale,
+                     long num_splits) {
+  CHECK_BF16_CUDA(x);
+  check_w8_weight(codes, wscale);
+  const long N = codes.size(0), K = codes.size(1);
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == K, "x must be [M,K], K = ", K);
+  const long M = x.size(0);
+  TORCH_CHECK(M >= 1 && M <= 64,
+              "linear_w8: the kernel serves 1 <= M <= 64 rows, got ", M);
+  TORCH_CHECK(num_splits >= 1 && num_splits <= 1024,
+              "linear_w8: num_splits out of range");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "linear_w8: x must be 16-byte aligned");
+  auto y = at::empty({M, N}, x.options());
+  at::Tensor ws;
+  float* wsp = nullptr;
+  if (num_splits > 1) {
+    ws = at::empty({num_splits * M * N}, x.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  TOK_HIP_OK(tok_linear_w8(x.data_ptr(), codes.data_ptr(),
+                           wscale.data_ptr<float>(), y.data_ptr(), wsp, (int)M,
+                           (int)N, (int)K, (int)num_splits, current_stream()));
+  return y;
+}
+
+// bf16(float(codes) * wscale[n]) as a [N,K] bf16 weight.
+at::Tensor w8_dequant(at::Tensor codes, at::Tensor wscale) {
+  check_w8_weight(codes, wscale);
+  auto out = at::empty(codes.sizes(), codes.options().dtype(at::kBFloat16));
+  TOK_HIP_OK(tok_w8_dequant(codes.data_ptr(), wscale.data_ptr<float>(),
+                            out.data_ptr(), codes.size(0), (int)codes.size(1),
+                            current_stream()));
+  return out;
+}
+
 // logits: [B, V] bf16, unit stride in V, any row stride. The per-row
 // parameters are [B] device tensors that the host never reads; u replaces
 // the generator's draw when given. Returns int64 [B].
@@ -1156,6 +1218,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "Quantize roped bf16 K/V rows into an e4m3 KV cache (gfx950)");
   mod.def("qkv_rope_append_fp8_", &qkv_rope_append_fp8_,
           "Multi-token packed-QKV RoPE + e4m3 KV-cache append (gfx950)");
+  mod.def("linear_w8", &linear_w8,
+          "Skinny-M linear over e4m3 weights with per-channel scales (gfx950)",
+          py::arg("x"), py::arg("codes"), py::arg("wscale"),
+          py::arg("num_splits"));
+  mod.def("w8_dequant", &w8_dequant,
+          "e4m3 weight codes * per-channel scale -> bf16 weight (gfx950)");
   mod.def("sample_tokens", &sample_tokens,
           "Fused temperature / top-k / top-p sampler (bf16, gfx950)",
           py::arg("logits"), py::arg("temperature"), py::arg("top_k"),

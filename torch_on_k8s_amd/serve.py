@@ -29,7 +29,10 @@ Endpoints:
                                   captured decode step, and the response
                                   carries the "seed" that was used;
                                   "kv_dtype": "fp8" keeps the KV cache in
-                                  e4m3 with per-row scales (ragged only)
+                                  e4m3 with per-row scales (ragged only);
+                                  "weight_dtype": "fp8" runs the projections
+                                  on e4m3 weights with per-channel scales
+                                  (ragged only)
 
 Prompts are token IDs: this framework is tokenizer-free by design
 (synthetic-data training; no network for vocab downloads).
@@ -116,12 +119,14 @@ class InferenceServer:
     def generate(self, prompt_ids, max_new_tokens: int = 32,
                  temperature: float = 0.0, ragged: bool = False,
                  eos_token_id=None, top_k: int = 0, top_p: float = 1.0,
-                 seed=None, prefill_chunk=None, kv_dtype=None):
+                 seed=None, prefill_chunk=None, kv_dtype=None,
+                 weight_dtype=None):
         import torch
         if ragged:
             return self._generate_ragged(prompt_ids, max_new_tokens,
                                          eos_token_id, temperature, top_k,
-                                         top_p, seed, prefill_chunk, kv_dtype)
+                                         top_p, seed, prefill_chunk, kv_dtype,
+                                         weight_dtype)
         dev = next(self.model.parameters()).device
         inp = torch.tensor(prompt_ids, dtype=torch.long, device=dev)
         t0 = time.perf_counter()
@@ -142,13 +147,15 @@ class InferenceServer:
 
     def _generate_ragged(self, prompt_ids, max_new_tokens, eos_token_id,
                          temperature=0.0, top_k=0, top_p=1.0, seed=None,
-                         prefill_chunk=None, kv_dtype=None):
+                         prefill_chunk=None, kv_dtype=None,
+                         weight_dtype=None):
         """Prompts of different lengths in one batch. new_tokens is the
         true count: a sequence that emitted eos stops there. A sampled
         request (temperature > 0) without a seed gets one here, and the
         response carries it: row b draws with seed + b. prefill_chunk, when
         given, prefills through the cache in chunks of that many tokens;
-        kv_dtype="fp8" keeps the KV cache in e4m3 with per-row scales."""
+        kv_dtype="fp8" keeps the KV cache in e4m3 with per-row scales;
+        weight_dtype="fp8" runs the projections on e4m3 weights."""
         import torch
         sampled = temperature > 0
         if sampled and seed is None:
@@ -161,7 +168,9 @@ class InferenceServer:
                 top_k=top_k, top_p=top_p, seed=seed,
                 **({} if prefill_chunk is None
                    else {"prefill_chunk": prefill_chunk}),
-                **({} if kv_dtype is None else {"kv_dtype": kv_dtype}))
+                **({} if kv_dtype is None else {"kv_dtype": kv_dtype}),
+                **({} if weight_dtype is None
+                   else {"weight_dtype": weight_dtype}))
         dt = time.perf_counter() - t0
         output_ids = [o.tolist() for o in outs]
         new_ids = [o[len(p):] for o, p in zip(output_ids, prompt_ids)]
@@ -193,6 +202,7 @@ def build_app(srv: InferenceServer):
         seed: int | None = None
         prefill_chunk: int | None = Field(default=None, ge=1)
         kv_dtype: str | None = None
+        weight_dtype: str | None = None
 
     app = FastAPI(title="torch-on-k8s-amd serving")
 
@@ -239,6 +249,8 @@ def build_app(srv: InferenceServer):
                      f"degrades silently")
         if req.kv_dtype not in (None, "fp8"):
             raise HTTPException(400, 'kv_dtype must be "fp8" or absent')
+        if req.weight_dtype not in (None, "fp8"):
+            raise HTTPException(400, 'weight_dtype must be "fp8" or absent')
         if req.kv_dtype is not None and req.prefill_chunk is not None:
             raise HTTPException(400, "kv_dtype and prefill_chunk do not "
                                      "combine: chunked prefill reads a bf16 "
@@ -250,7 +262,8 @@ def build_app(srv: InferenceServer):
                                 top_k=req.top_k, top_p=req.top_p,
                                 seed=req.seed,
                                 prefill_chunk=req.prefill_chunk,
-                                kv_dtype=req.kv_dtype)
+                                kv_dtype=req.kv_dtype,
+                                weight_dtype=req.weight_dtype)
         except NotImplementedError as e:
             raise HTTPException(400, str(e))
 
@@ -274,6 +287,8 @@ def build_app(srv: InferenceServer):
             raise HTTPException(400, 'prefill_chunk needs "ragged": true')
         if req.kv_dtype is not None:
             raise HTTPException(400, 'kv_dtype needs "ragged": true')
+        if req.weight_dtype is not None:
+            raise HTTPException(400, 'weight_dtype needs "ragged": true')
         if len({len(p) for p in req.prompt_ids}) != 1:
             raise HTTPException(400, "all prompts must share one length")
         if vocab and any(t < 0 or t >= vocab
