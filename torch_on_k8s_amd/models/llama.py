@@ -382,7 +382,8 @@ class LlamaModel(nn.Module):
                         seed=None,
                         prefill_chunk: int | None = None,
                         kv_dtype: str | None = None,
-                        weight_dtype: str | None = None
+                        weight_dtype: str | None = None,
+                        kv_page_size: int | None = None
                         ) -> list[torch.Tensor]:
         """Generation for prompts of different lengths (each a 1-D id
         tensor or a list of ids, length >= 1). Returns one 1-D tensor per
@@ -432,7 +433,25 @@ class LlamaModel(nn.Module):
         requantized; drop_quantized_weights() frees them. The bf16 weights
         stay resident, and the embedding lookup stays bf16 also with
         tie_embeddings. None (the default) is the bf16 path. Combines with
-        kv_dtype, prefill_chunk and the sampling arguments."""
+        kv_dtype, prefill_chunk and the sampling arguments.
+
+        kv_page_size=64 keeps the KV cache in pages of 64 tokens instead of
+        a [B, S0max + max_new_tokens] rectangle: per layer a pool
+        [P, Hkv, 64, D] of exactly ops.kv_pages_needed(lens, max_new_tokens)
+        pages, and one int32 page table [B, NP] on the device shared by all
+        layers (unused entries -1; a sequence's pages are dealt round-robin
+        over the sequences). The padded prefill stores its k / v into the
+        pool; prefill_chunk and the decode step, eager and captured, go
+        through ops.qkv_rope_append_paged_ + ops.attention_paged. None (the
+        default) is the rectangle. Combines with prefill_chunk, weight_dtype
+        and the sampling arguments; not with kv_dtype="fp8"."""
+        if kv_page_size is not None and kv_page_size != ops.KV_PAGE:
+            raise ValueError(f"kv_page_size must be None or {ops.KV_PAGE}, "
+                             f"got {kv_page_size!r}")
+        paged = kv_page_size is not None
+        if paged and kv_dtype is not None:
+            raise ValueError("kv_page_size does not combine with kv_dtype: "
+                             "the paged pool is bf16")
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1 or None")
         if kv_dtype not in (None, "fp8"):
@@ -516,9 +535,30 @@ class LlamaModel(nn.Module):
         for b, s in enumerate(seqs):
             input_ids[b, :s.numel()] = s
         cache_dtype = torch.float8_e4m3fn if fp8 else dtype
-        kc = [torch.zeros(B, Tmax, Hkv, D, dtype=cache_dtype, device=dev)
+        if paged:
+            # kc / vc are the pools; pages dealt round-robin over sequences
+            PG = ops.KV_PAGE
+            need = [-(-(s.numel() + max_new_tokens) // PG) for s in seqs]
+            n_pages = ops.kv_pages_needed([s.numel() for s in seqs],
+                                          max_new_tokens)
+            table = [[-1] * max(need) for _ in range(B)]
+            nxt = 0
+            for j in range(max(need)):
+                for b in range(B):
+                    if j < need[b]:
+                        table[b][j] = nxt
+                        nxt += 1
+            page_table = torch.tensor(table, dtype=torch.int32, device=dev)
+            assert nxt == n_pages
+            self._kv_pool_pages = nxt         # pages dealt by the last call
+            Tmax = PG * max(need)             # the table's span (rope rows)
+            cache_shape = (n_pages, Hkv, PG, D)
+            one32 = torch.ones(B, dtype=torch.int32, device=dev)
+        else:
+            cache_shape = (B, Tmax, Hkv, D)
+        kc = [torch.zeros(cache_shape, dtype=cache_dtype, device=dev)
               for _ in self.layers]
-        vc = [torch.zeros(B, Tmax, Hkv, D, dtype=cache_dtype, device=dev)
+        vc = [torch.zeros(cache_shape, dtype=cache_dtype, device=dev)
               for _ in self.layers]
         if fp8:
             ks = [torch.zeros(B, Tmax, Hkv, device=dev) for _ in self.layers]
@@ -530,6 +570,11 @@ class LlamaModel(nn.Module):
         if prefill_chunk is None:
             # prefill over the padded rectangle
             x = self.embed_tokens(input_ids)
+            if paged:  # where every prompt row goes: (page, slot)
+                bi = torch.cat([torch.full((s.numel(),), b)
+                                for b, s in enumerate(seqs)]).to(dev)
+                ti = torch.cat([torch.arange(s.numel()) for s in seqs]).to(dev)
+                pg_i = page_table[bi, ti // PG].long()
             cs0, sn0 = cos[:S0].contiguous(), sin[:S0].contiguous()
             for i, blk in enumerate(self.layers):
                 if w8:
@@ -543,6 +588,9 @@ class LlamaModel(nn.Module):
                     ops.kv_quantize_append_(k, v, zero32,
                                             lens0.to(torch.int32), kc[i],
                                             vc[i], ks[i], vs[i])
+                elif paged:
+                    kc[i][pg_i, :, ti % PG] = k[bi, ti]
+                    vc[i][pg_i, :, ti % PG] = v[bi, ti]
                 else:
                     kc[i][:, :S0] = k
                     vc[i][:, :S0] = v
@@ -567,9 +615,17 @@ class LlamaModel(nn.Module):
                 x = self.embed_tokens(ids)
                 for i, blk in enumerate(self.layers):
                     qkv = lin(blk.attn.qkv_proj, blk.input_norm(x))
-                    q = ops.qkv_rope_append_chunk_(qkv, cos, sin, cpos, cql,
-                                                   kc[i], vc[i], Hq, Hkv, D)
-                    o = ops.attention_extend(q, kc[i], vc[i], clen, cql)
+                    if paged:
+                        q = ops.qkv_rope_append_paged_(
+                            qkv, cos, sin, cpos, cql, kc[i], vc[i],
+                            page_table, Hq, Hkv, D)
+                        o = ops.attention_paged(q, kc[i], vc[i], page_table,
+                                                clen, cql)
+                    else:
+                        q = ops.qkv_rope_append_chunk_(
+                            qkv, cos, sin, cpos, cql, kc[i], vc[i], Hq, Hkv,
+                            D)
+                        o = ops.attention_extend(q, kc[i], vc[i], clen, cql)
                     x = x + lin(blk.attn.o_proj, o.reshape(B, N, Hq * D))
                     x = x + mlp(blk, blk.post_attn_norm(x))
                 # the chunk that holds a sequence's last prompt token
@@ -602,6 +658,12 @@ class LlamaModel(nn.Module):
                         vs[i], Hq, Hkv, D).view(B, Hq, D)
                     o = ops.attention_decode_ragged(
                         q, kc[i], vc[i], lens, kscale=ks[i], vscale=vs[i])
+                elif paged:
+                    q = ops.qkv_rope_append_paged_(
+                        qkv, cos, sin, pos, one32, kc[i], vc[i], page_table,
+                        Hq, Hkv, D)
+                    o = ops.attention_paged(q, kc[i], vc[i], page_table,
+                                            lens, one32)
                 else:
                     q = ops.qkv_rope_append_(
                         qkv.view(B, (Hq + 2 * Hkv) * D), cos, sin, pos,

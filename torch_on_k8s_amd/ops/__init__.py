@@ -824,6 +824,91 @@ def qkv_rope_append_chunk_(qkv: torch.Tensor, cos: torch.Tensor,
 
 
 # --------------------------------------------------------------------------
+# Paged KV cache: pools [P, Hkv, 64, D] and a page table [B, NP] on the device
+# --------------------------------------------------------------------------
+KV_PAGE = 64                   # tokens per page = keys per attention tile
+
+
+def kv_pages_needed(lens, max_new_tokens: int) -> int:
+    """Pages a pool must hold for prompts of these lengths plus
+    max_new_tokens each: sum(ceil((len_b + max_new_tokens) / 64))."""
+    return sum(-(-(int(n) + int(max_new_tokens)) // KV_PAGE) for n in lens)
+
+
+def _gather_pages(pool: torch.Tensor, page_table: torch.Tensor):
+    """[P, Hkv, 64, D] -> the contiguous cache [B, 64 NP, Hkv, D] the table
+    describes (an id outside [0, P) is clamped, as the kernel clamps it)."""
+    B, NP = page_table.shape
+    pages = pool[page_table.long().clamp(0, pool.shape[0] - 1)]
+    return pages.permute(0, 1, 3, 2, 4).reshape(
+        B, NP * KV_PAGE, pool.shape[1], pool.shape[3])
+
+
+@torch.no_grad()
+def attention_paged(q: torch.Tensor, kpool: torch.Tensor,
+                    vpool: torch.Tensor, page_table: torch.Tensor,
+                    lens: torch.Tensor, qlens: torch.Tensor, *,
+                    num_splits: int | None = None) -> torch.Tensor:
+    """attention_extend over a paged cache. q: [B, Tq, Hq, D]; kpool/vpool:
+    [P, Hkv, 64, D]; page_table: [B, NP] int32 and lens, qlens: [B] int32 on
+    q's device. Logical row t of sequence b lives in page
+    page_table[b, t // 64], slot t % 64; the contract is attention_extend's
+    with Tmax = 64 * NP. A page id outside [0, P) is clamped (wrong numbers,
+    never a fault). The host reads neither the table nor the lengths, so the
+    call can be captured and a replay follows new contents. Up to 16 packed
+    rows (Tq * Hq/Hkv, decode is Tq = 1) run the key-split MFMA layout, more
+    the row layout. Returns [B, Tq, Hq, D]."""
+    B, Tq, Hq, D = q.shape
+    Hkv, NP = kpool.shape[1], page_table.shape[1]
+    Tmax = KV_PAGE * NP
+    if num_splits is None:
+        num_splits = extend_splits(B, Hkv, Tq, max(1, Hq // max(1, Hkv)),
+                                   Tmax)
+    if q.is_cuda:  # the binding refuses unsupported D, Hq/Hkv and page size
+        return _require_ext("attention_paged").attn_paged(
+            q.contiguous(), kpool, vpool, page_table, lens, qlens,
+            int(num_splits), extend_chunk(Tmax, num_splits))
+    if kpool.dim() != 4 or kpool.shape[2] != KV_PAGE:
+        raise ValueError(f"the page size must be {KV_PAGE} tokens")
+    return attention_extend(q, _gather_pages(kpool, page_table),
+                            _gather_pages(vpool, page_table), lens, qlens)
+
+
+@torch.no_grad()
+def qkv_rope_append_paged_(qkv: torch.Tensor, cos: torch.Tensor,
+                           sin: torch.Tensor, pos: torch.Tensor,
+                           qlens: torch.Tensor, kpool: torch.Tensor,
+                           vpool: torch.Tensor, page_table: torch.Tensor,
+                           Hq: int, Hkv: int, D: int) -> torch.Tensor:
+    """qkv_rope_append_chunk_ into a paged cache: token i of sequence b is
+    rotated at p = pos[b] + i and its k and v written to slot p % 64 of page
+    page_table[b, p // 64], in place. A token is live iff i < qlens[b],
+    0 <= p < 64 * NP and its table entry is in [0, P); a dead token writes
+    nothing and gets a zero q row. Returns q [B, Tq, Hq, D]."""
+    if qkv.is_cuda:
+        return _require_ext("qkv_rope_append_paged").qkv_rope_append_paged_(
+            qkv.contiguous(), cos, sin, pos, qlens, kpool, vpool, page_table,
+            Hq, Hkv, D)
+    if kpool.dim() != 4 or kpool.shape[2] != KV_PAGE:
+        raise ValueError(f"the page size must be {KV_PAGE} tokens")
+    B, Tq = qkv.shape[0], qkv.shape[1]
+    P, NP = kpool.shape[0], page_table.shape[1]
+    kc = _gather_pages(kpool, page_table)
+    vc = _gather_pages(vpool, page_table)
+    q = qkv_rope_append_chunk_(qkv, cos, sin, pos, qlens, kc, vc, Hq, Hkv, D)
+    i = torch.arange(Tq).view(1, Tq)
+    at = pos.long().view(B, 1) + i
+    live = (i < qlens.view(B, 1)) & (at >= 0) & (at < KV_PAGE * NP)
+    p = at.clamp(0, KV_PAGE * NP - 1)
+    pid = page_table.long().gather(1, p // KV_PAGE)
+    live &= (pid >= 0) & (pid < P)
+    bi, ti = torch.nonzero(live, as_tuple=True)
+    kpool[pid[bi, ti], :, p[bi, ti] % KV_PAGE] = kc[bi, p[bi, ti]]
+    vpool[pid[bi, ti], :, p[bi, ti] % KV_PAGE] = vc[bi, p[bi, ti]]
+    return q.masked_fill(~live.view(B, Tq, 1, 1), 0)
+
+
+# --------------------------------------------------------------------------
 # FP8 (OCP e4m3) KV cache: codes [B,Tmax,Hkv,D] + one fp32 scale per row
 # --------------------------------------------------------------------------
 FP8_MAX = 448.0
@@ -1564,6 +1649,7 @@ __all__ = [
     "decode_ragged_splits", "decode_ragged_chunk",
     "attention_extend", "qkv_rope_append_chunk_",
     "extend_splits", "extend_chunk",
+    "KV_PAGE", "kv_pages_needed", "attention_paged", "qkv_rope_append_paged_",
     "sample_tokens", "sample_uniform", "philox4x32_10",
     "linear_w8", "linear_w8_splits", "quantize_weight_fp8", "w8_dequant",
 ]

@@ -30,6 +30,8 @@ Endpoints:
                                   carries the "seed" that was used;
                                   "kv_dtype": "fp8" keeps the KV cache in
                                   e4m3 with per-row scales (ragged only);
+                                  "kv_page_size": 64 keeps the KV cache in
+                                  64-token pages (ragged only);
                                   "weight_dtype": "fp8" runs the projections
                                   on e4m3 weights with per-channel scales
                                   (ragged only)
@@ -120,13 +122,13 @@ class InferenceServer:
                  temperature: float = 0.0, ragged: bool = False,
                  eos_token_id=None, top_k: int = 0, top_p: float = 1.0,
                  seed=None, prefill_chunk=None, kv_dtype=None,
-                 weight_dtype=None):
+                 weight_dtype=None, kv_page_size=None):
         import torch
         if ragged:
             return self._generate_ragged(prompt_ids, max_new_tokens,
                                          eos_token_id, temperature, top_k,
                                          top_p, seed, prefill_chunk, kv_dtype,
-                                         weight_dtype)
+                                         weight_dtype, kv_page_size)
         dev = next(self.model.parameters()).device
         inp = torch.tensor(prompt_ids, dtype=torch.long, device=dev)
         t0 = time.perf_counter()
@@ -148,14 +150,15 @@ class InferenceServer:
     def _generate_ragged(self, prompt_ids, max_new_tokens, eos_token_id,
                          temperature=0.0, top_k=0, top_p=1.0, seed=None,
                          prefill_chunk=None, kv_dtype=None,
-                         weight_dtype=None):
+                         weight_dtype=None, kv_page_size=None):
         """Prompts of different lengths in one batch. new_tokens is the
         true count: a sequence that emitted eos stops there. A sampled
         request (temperature > 0) without a seed gets one here, and the
         response carries it: row b draws with seed + b. prefill_chunk, when
         given, prefills through the cache in chunks of that many tokens;
         kv_dtype="fp8" keeps the KV cache in e4m3 with per-row scales;
-        weight_dtype="fp8" runs the projections on e4m3 weights."""
+        weight_dtype="fp8" runs the projections on e4m3 weights;
+        kv_page_size=64 keeps the KV cache in 64-token pages."""
         import torch
         sampled = temperature > 0
         if sampled and seed is None:
@@ -170,7 +173,9 @@ class InferenceServer:
                    else {"prefill_chunk": prefill_chunk}),
                 **({} if kv_dtype is None else {"kv_dtype": kv_dtype}),
                 **({} if weight_dtype is None
-                   else {"weight_dtype": weight_dtype}))
+                   else {"weight_dtype": weight_dtype}),
+                **({} if kv_page_size is None
+                   else {"kv_page_size": kv_page_size}))
         dt = time.perf_counter() - t0
         output_ids = [o.tolist() for o in outs]
         new_ids = [o[len(p):] for o, p in zip(output_ids, prompt_ids)]
@@ -203,6 +208,7 @@ def build_app(srv: InferenceServer):
         prefill_chunk: int | None = Field(default=None, ge=1)
         kv_dtype: str | None = None
         weight_dtype: str | None = None
+        kv_page_size: int | None = None
 
     app = FastAPI(title="torch-on-k8s-amd serving")
 
@@ -251,6 +257,11 @@ def build_app(srv: InferenceServer):
             raise HTTPException(400, 'kv_dtype must be "fp8" or absent')
         if req.weight_dtype not in (None, "fp8"):
             raise HTTPException(400, 'weight_dtype must be "fp8" or absent')
+        if req.kv_page_size not in (None, 64):
+            raise HTTPException(400, "kv_page_size must be 64 or absent")
+        if req.kv_page_size is not None and req.kv_dtype is not None:
+            raise HTTPException(400, "kv_page_size and kv_dtype do not "
+                                     "combine: the paged pool is bf16")
         if req.kv_dtype is not None and req.prefill_chunk is not None:
             raise HTTPException(400, "kv_dtype and prefill_chunk do not "
                                      "combine: chunked prefill reads a bf16 "
@@ -263,7 +274,8 @@ def build_app(srv: InferenceServer):
                                 seed=req.seed,
                                 prefill_chunk=req.prefill_chunk,
                                 kv_dtype=req.kv_dtype,
-                                weight_dtype=req.weight_dtype)
+                                weight_dtype=req.weight_dtype,
+                                kv_page_size=req.kv_page_size)
         except NotImplementedError as e:
             raise HTTPException(400, str(e))
 
@@ -289,6 +301,8 @@ def build_app(srv: InferenceServer):
             raise HTTPException(400, 'kv_dtype needs "ragged": true')
         if req.weight_dtype is not None:
             raise HTTPException(400, 'weight_dtype needs "ragged": true')
+        if req.kv_page_size is not None:
+            raise HTTPException(400, 'kv_page_size needs "ragged": true')
         if len({len(p) for p in req.prompt_ids}) != 1:
             raise HTTPException(400, "all prompts must share one length")
         if vocab and any(t < 0 or t >= vocab
