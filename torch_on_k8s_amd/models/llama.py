@@ -444,19 +444,31 @@ class LlamaModel(nn.Module):
         pool; prefill_chunk and the decode step, eager and captured, go
         through ops.qkv_rope_append_paged_ + ops.attention_paged. None (the
         default) is the rectangle. Combines with prefill_chunk, weight_dtype
-        and the sampling arguments; not with kv_dtype="fp8"."""
+        and the sampling arguments; not with kv_dtype="fp8".
+
+        kv_dtype="fp8_paged" is both at once: per layer e4m3 code pools
+        [P, Hkv, 64, D] and fp32 scale pools [P, Hkv, 64] of exactly
+        ops.kv_pages_needed pages under the page table of the bf16 paged
+        mode, each row quantized as kv_dtype="fp8" quantizes it. The padded
+        prefill stores through ops.kv_quantize_append_paged_; prefill_chunk
+        and the decode step, eager and captured, go through
+        ops.qkv_rope_append_paged_fp8_ + the fp8 ops.attention_paged.
+        Combines with prefill_chunk, weight_dtype and the sampling
+        arguments; kv_page_size may be None or 64 with it."""
         if kv_page_size is not None and kv_page_size != ops.KV_PAGE:
             raise ValueError(f"kv_page_size must be None or {ops.KV_PAGE}, "
                              f"got {kv_page_size!r}")
-        paged = kv_page_size is not None
+        if kv_dtype not in (None, "fp8", "fp8_paged"):
+            raise ValueError(f"kv_dtype must be None, 'fp8' or 'fp8_paged', "
+                             f"got {kv_dtype!r}")
+        fp8p = kv_dtype == "fp8_paged"
+        paged = kv_page_size is not None and not fp8p   # the bf16 pool
         if paged and kv_dtype is not None:
             raise ValueError("kv_page_size does not combine with kv_dtype: "
-                             "the paged pool is bf16")
+                             "the paged pool is bf16 (the e4m3 pool is "
+                             "kv_dtype='fp8_paged')")
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1 or None")
-        if kv_dtype not in (None, "fp8"):
-            raise ValueError(f"kv_dtype must be None or 'fp8', got "
-                             f"{kv_dtype!r}")
         if weight_dtype not in (None, "fp8"):
             raise ValueError(f"weight_dtype must be None or 'fp8', got "
                              f"{weight_dtype!r}")
@@ -464,7 +476,8 @@ class LlamaModel(nn.Module):
         fp8 = kv_dtype == "fp8"
         if fp8 and prefill_chunk is not None:
             raise ValueError("kv_dtype='fp8' has no chunked prefill: "
-                             "attention_extend reads a bf16 cache")
+                             "attention_extend reads a bf16 cache "
+                             "(kv_dtype='fp8_paged' has one)")
         cfg = self.cfg
         dev = self.embed_tokens.weight.device
         dtype = self.embed_tokens.weight.dtype
@@ -534,8 +547,8 @@ class LlamaModel(nn.Module):
                                device=dev)
         for b, s in enumerate(seqs):
             input_ids[b, :s.numel()] = s
-        cache_dtype = torch.float8_e4m3fn if fp8 else dtype
-        if paged:
+        cache_dtype = torch.float8_e4m3fn if fp8 or fp8p else dtype
+        if paged or fp8p:
             # kc / vc are the pools; pages dealt round-robin over sequences
             PG = ops.KV_PAGE
             need = [-(-(s.numel() + max_new_tokens) // PG) for s in seqs]
@@ -565,6 +578,12 @@ class LlamaModel(nn.Module):
             vs = [torch.zeros(B, Tmax, Hkv, device=dev) for _ in self.layers]
             zero32 = torch.zeros(B, dtype=torch.int32, device=dev)
             one32 = torch.ones(B, dtype=torch.int32, device=dev)
+        if fp8p:
+            ks = [torch.zeros(cache_shape[:3], device=dev)
+                  for _ in self.layers]
+            vs = [torch.zeros(cache_shape[:3], device=dev)
+                  for _ in self.layers]
+            zero32 = torch.zeros(B, dtype=torch.int32, device=dev)
         cos, sin = build_rope_table(cfg, Tmax, dev)
 
         if prefill_chunk is None:
@@ -588,6 +607,10 @@ class LlamaModel(nn.Module):
                     ops.kv_quantize_append_(k, v, zero32,
                                             lens0.to(torch.int32), kc[i],
                                             vc[i], ks[i], vs[i])
+                elif fp8p:
+                    ops.kv_quantize_append_paged_(
+                        k, v, zero32, lens0.to(torch.int32), kc[i], vc[i],
+                        ks[i], vs[i], page_table)
                 elif paged:
                     kc[i][pg_i, :, ti % PG] = k[bi, ti]
                     vc[i][pg_i, :, ti % PG] = v[bi, ti]
@@ -615,7 +638,14 @@ class LlamaModel(nn.Module):
                 x = self.embed_tokens(ids)
                 for i, blk in enumerate(self.layers):
                     qkv = lin(blk.attn.qkv_proj, blk.input_norm(x))
-                    if paged:
+                    if fp8p:
+                        q = ops.qkv_rope_append_paged_fp8_(
+                            qkv, cos, sin, cpos, cql, kc[i], vc[i], ks[i],
+                            vs[i], page_table, Hq, Hkv, D)
+                        o = ops.attention_paged(
+                            q, kc[i], vc[i], page_table, clen, cql,
+                            kscale=ks[i], vscale=vs[i])
+                    elif paged:
                         q = ops.qkv_rope_append_paged_(
                             qkv, cos, sin, cpos, cql, kc[i], vc[i],
                             page_table, Hq, Hkv, D)
@@ -658,6 +688,13 @@ class LlamaModel(nn.Module):
                         vs[i], Hq, Hkv, D).view(B, Hq, D)
                     o = ops.attention_decode_ragged(
                         q, kc[i], vc[i], lens, kscale=ks[i], vscale=vs[i])
+                elif fp8p:
+                    q = ops.qkv_rope_append_paged_fp8_(
+                        qkv, cos, sin, pos, one32, kc[i], vc[i], ks[i],
+                        vs[i], page_table, Hq, Hkv, D)
+                    o = ops.attention_paged(
+                        q, kc[i], vc[i], page_table, lens, one32,
+                        kscale=ks[i], vscale=vs[i])
                 elif paged:
                     q = ops.qkv_rope_append_paged_(
                         qkv, cos, sin, pos, one32, kc[i], vc[i], page_table,

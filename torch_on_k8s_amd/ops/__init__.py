@@ -844,10 +844,35 @@ def _gather_pages(pool: torch.Tensor, page_table: torch.Tensor):
         B, NP * KV_PAGE, pool.shape[1], pool.shape[3])
 
 
+def _gather_pages_fp8(pool: torch.Tensor, scale: torch.Tensor,
+                      page_table: torch.Tensor):
+    """e4m3 pool [P, Hkv, 64, D] and its scales [P, Hkv, 64] -> the
+    contiguous (codes [B, 64 NP, Hkv, D], scales [B, 64 NP, Hkv])."""
+    codes = _gather_pages(pool.view(torch.uint8), page_table)
+    sc = _gather_pages(scale.unsqueeze(-1), page_table).squeeze(-1)
+    return codes.view(torch.float8_e4m3fn), sc
+
+
+def _check_fp8_pool(kpool, vpool, kscale, vscale):
+    for t in (kpool, vpool):
+        if (t.dtype != torch.float8_e4m3fn or t.dim() != 4
+                or t.shape[2] != KV_PAGE):
+            raise ValueError(f"fp8 pools must be float8_e4m3fn "
+                             f"[P, Hkv, {KV_PAGE}, D]")
+    if kpool.shape != vpool.shape:
+        raise ValueError("pool shape mismatch")
+    for t in (kscale, vscale):
+        if t.dtype != torch.float32 or tuple(t.shape) != tuple(kpool.shape[:3]):
+            raise ValueError(f"kscale and vscale must be fp32 "
+                             f"[P, Hkv, {KV_PAGE}]")
+
+
 @torch.no_grad()
 def attention_paged(q: torch.Tensor, kpool: torch.Tensor,
                     vpool: torch.Tensor, page_table: torch.Tensor,
                     lens: torch.Tensor, qlens: torch.Tensor, *,
+                    kscale: torch.Tensor | None = None,
+                    vscale: torch.Tensor | None = None,
                     num_splits: int | None = None) -> torch.Tensor:
     """attention_extend over a paged cache. q: [B, Tq, Hq, D]; kpool/vpool:
     [P, Hkv, 64, D]; page_table: [B, NP] int32 and lens, qlens: [B] int32 on
@@ -857,19 +882,42 @@ def attention_paged(q: torch.Tensor, kpool: torch.Tensor,
     never a fault). The host reads neither the table nor the lengths, so the
     call can be captured and a replay follows new contents. Up to 16 packed
     rows (Tq * Hq/Hkv, decode is Tq = 1) run the key-split MFMA layout, more
-    the row layout. Returns [B, Tq, Hq, D]."""
+    the row layout. Returns [B, Tq, Hq, D].
+
+    torch.float8_e4m3fn pools need kscale/vscale [P, Hkv, 64] fp32 (one
+    scale per (page, kv head, slot); an element means float(code) * scale,
+    the quantizer is quantize_rows_fp8) and run attn_paged_fp8_kernel: both
+    products on the bf16 MFMAs over the codes, the scales folded in once per
+    key. bf16 pools take no scales."""
     B, Tq, Hq, D = q.shape
     Hkv, NP = kpool.shape[1], page_table.shape[1]
     Tmax = KV_PAGE * NP
+    fp8 = kpool.dtype == torch.float8_e4m3fn
+    if fp8 and (kscale is None or vscale is None):
+        raise ValueError("fp8 pools need kscale and vscale")
+    if not fp8 and (kscale is not None or vscale is not None):
+        raise ValueError(f"kscale/vscale go with float8_e4m3fn pools, got "
+                         f"{kpool.dtype}")
+    if fp8:
+        _check_fp8_pool(kpool, vpool, kscale, vscale)
     if num_splits is None:
         num_splits = extend_splits(B, Hkv, Tq, max(1, Hq // max(1, Hkv)),
                                    Tmax)
+    if q.is_cuda and fp8:
+        return _require_ext("attention_paged").attn_paged_fp8(
+            q.contiguous(), kpool, vpool, kscale, vscale, page_table, lens,
+            qlens, int(num_splits), extend_chunk(Tmax, num_splits))
     if q.is_cuda:  # the binding refuses unsupported D, Hq/Hkv and page size
         return _require_ext("attention_paged").attn_paged(
             q.contiguous(), kpool, vpool, page_table, lens, qlens,
             int(num_splits), extend_chunk(Tmax, num_splits))
     if kpool.dim() != 4 or kpool.shape[2] != KV_PAGE:
         raise ValueError(f"the page size must be {KV_PAGE} tokens")
+    if fp8:  # dequantized to fp32, then the math of attention_extend
+        kc, ks = _gather_pages_fp8(kpool, kscale, page_table)
+        vc, vs = _gather_pages_fp8(vpool, vscale, page_table)
+        return attention_extend(q, kc.float() * ks.unsqueeze(-1),
+                                vc.float() * vs.unsqueeze(-1), lens, qlens)
     return attention_extend(q, _gather_pages(kpool, page_table),
                             _gather_pages(vpool, page_table), lens, qlens)
 
@@ -917,8 +965,8 @@ FP8_MAX = 448.0
 def kv_cache_bytes_per_token(Hkv: int, D: int, layers: int,
                              kv_dtype: str | None = None) -> int:
     """K + V bytes one token occupies over all layers: bf16, or e4m3 codes
-    plus the fp32 row scales."""
-    per_row = D + 4 if kv_dtype == "fp8" else 2 * D
+    plus the fp32 row scales ("fp8" and "fp8_paged" alike)."""
+    per_row = D + 4 if kv_dtype in ("fp8", "fp8_paged") else 2 * D
     return 2 * layers * Hkv * per_row
 
 
@@ -1017,6 +1065,90 @@ def qkv_rope_append_fp8_(qkv: torch.Tensor, cos: torch.Tensor,
         codes, sc = quantize_rows_fp8(rows[bi, pi])
         _fp8_store(cache, scale, codes, sc, bi, pi)
     return q
+
+
+# --------------------------------------------------------------------------
+# FP8 paged KV cache: code pools [P,Hkv,64,D] e4m3 + scale pools [P,Hkv,64]
+# --------------------------------------------------------------------------
+def _live_pages(pos, qlens, Tq, page_table, P):
+    """(live [B,Tq], position [B,Tq], page id [B,Tq]) of Tq tokens per
+    sequence from pos[b]: the liveness rule of the paged appends."""
+    B, NP = page_table.shape
+    i = torch.arange(Tq).view(1, Tq)
+    at = pos.long().view(B, 1) + i
+    live = (i < qlens.view(B, 1)) & (at >= 0) & (at < KV_PAGE * NP)
+    p = at.clamp(0, KV_PAGE * NP - 1)
+    pid = page_table.long().gather(1, p // KV_PAGE)
+    return live & (pid >= 0) & (pid < P), p, pid
+
+
+def _fp8_paged_append(append, Tq, pos, qlens, kpool, vpool, kscale, vscale,
+                      page_table):
+    """Run a contiguous fp8 append on the caches gathered through the table
+    and copy the live tokens' rows back into their pages."""
+    _check_fp8_pool(kpool, vpool, kscale, vscale)
+    kc, ks = _gather_pages_fp8(kpool, kscale, page_table)
+    vc, vs = _gather_pages_fp8(vpool, vscale, page_table)
+    kc, vc = kc.contiguous(), vc.contiguous()
+    ks, vs = ks.contiguous(), vs.contiguous()
+    out = append(kc, vc, ks, vs)
+    live, p, pid = _live_pages(pos, qlens, Tq, page_table, kpool.shape[0])
+    bi, ti = torch.nonzero(live, as_tuple=True)
+    pg, sl, at = pid[bi, ti], p[bi, ti] % KV_PAGE, p[bi, ti]
+    for pool, scale, c, s in ((kpool, kscale, kc, ks), (vpool, vscale, vc, vs)):
+        pool.view(torch.uint8)[pg, :, sl] = c.view(torch.uint8)[bi, at]
+        scale[pg, :, sl] = s[bi, at]
+    return out, live
+
+
+@torch.no_grad()
+def kv_quantize_append_paged_(k: torch.Tensor, v: torch.Tensor,
+                              pos: torch.Tensor, qlens: torch.Tensor,
+                              kpool: torch.Tensor, vpool: torch.Tensor,
+                              kscale: torch.Tensor, vscale: torch.Tensor,
+                              page_table: torch.Tensor) -> None:
+    """kv_quantize_append_ into an e4m3 paged cache: token i of sequence b
+    (k, v [B, Tq, Hkv, D] bf16, k already roped) is quantized
+    (quantize_rows_fp8) into slot p % 64 of page page_table[b, p // 64],
+    p = pos[b] + i, codes into kpool/vpool [P, Hkv, 64, D] and the row scale
+    into kscale/vscale [P, Hkv, 64], in place. A token is live iff
+    i < qlens[b], 0 <= p < 64 * NP and its table entry is in [0, P); a dead
+    token writes neither codes nor scales."""
+    if k.is_cuda:
+        _require_ext("kv_quantize_append_paged").kv_quantize_append_paged_(
+            k.contiguous(), v.contiguous(), pos, qlens, kpool, vpool, kscale,
+            vscale, page_table)
+        return
+    if k.dim() != 4 or k.shape != v.shape:
+        raise ValueError("k and v must be [B, Tq, Hkv, D]")
+    _fp8_paged_append(
+        lambda kc, vc, ks, vs: kv_quantize_append_(k, v, pos, qlens, kc, vc,
+                                                   ks, vs),
+        k.shape[1], pos, qlens, kpool, vpool, kscale, vscale, page_table)
+
+
+@torch.no_grad()
+def qkv_rope_append_paged_fp8_(qkv: torch.Tensor, cos: torch.Tensor,
+                               sin: torch.Tensor, pos: torch.Tensor,
+                               qlens: torch.Tensor, kpool: torch.Tensor,
+                               vpool: torch.Tensor, kscale: torch.Tensor,
+                               vscale: torch.Tensor,
+                               page_table: torch.Tensor, Hq: int, Hkv: int,
+                               D: int) -> torch.Tensor:
+    """qkv_rope_append_fp8_ into an e4m3 paged cache: the same q, codes and
+    scales for the same token, the destination looked up in the table as
+    qkv_rope_append_paged_ does, with its liveness rule. Returns bf16 q
+    [B, Tq, Hq, D], a zero row for a dead token."""
+    if qkv.is_cuda:
+        return _require_ext(
+            "qkv_rope_append_paged_fp8").qkv_rope_append_paged_fp8_(
+            qkv.contiguous(), cos, sin, pos, qlens, kpool, vpool, kscale,
+            vscale, page_table, Hq, Hkv, D)
+    q, live = _fp8_paged_append(
+        lambda kc, vc, ks, vs: qkv_rope_append_fp8_(
+            qkv, cos, sin, pos, qlens, kc, vc, ks, vs, Hq, Hkv, D),
+        qkv.shape[1], pos, qlens, kpool, vpool, kscale, vscale, page_table)
+    return q.masked_fill(~live.view(*live.shape, 1, 1), 0)
 
 
 # --------------------------------------------------------------------------
@@ -1650,6 +1782,7 @@ __all__ = [
     "attention_extend", "qkv_rope_append_chunk_",
     "extend_splits", "extend_chunk",
     "KV_PAGE", "kv_pages_needed", "attention_paged", "qkv_rope_append_paged_",
+    "qkv_rope_append_paged_fp8_", "kv_quantize_append_paged_",
     "sample_tokens", "sample_uniform", "philox4x32_10",
     "linear_w8", "linear_w8_splits", "quantize_weight_fp8", "w8_dequant",
 ]

@@ -116,6 +116,25 @@ hipError_t tok_qkv_rope_append_paged(const void* qkv, void* q, void* kpool,
                                      const int* qlens, const int* page_table,
                                      int B, int Tq, int NP, int P, int Hq,
                                      int Hkv, int D, hipStream_t stream);
+hipError_t tok_attn_paged_fp8(const void* q, const void* kpool,
+                              const void* vpool, const float* kscale,
+                              const float* vscale, const int* page_table,
+                              const int* lens, const int* qlens, void* out,
+                              float* ws, int B, int Tq, int NP, int P, int Hq,
+                              int Hkv, int D, int num_splits, int chunk,
+                              hipStream_t stream);
+hipError_t tok_kv_quantize_append_paged(const void* k, const void* v,
+                                        void* kpool, void* vpool,
+                                        float* kscale, float* vscale,
+                                        const int* pos, const int* qlens,
+                                        const int* page_table, int B, int Tq,
+                                        int NP, int P, int Hkv, int D,
+                                        hipStream_t stream);
+hipError_t tok_qkv_rope_append_paged_fp8(
+    const void* qkv, void* q, void* kpool, void* vpool, float* kscale,
+    float* vscale, const float* cos_tab, const float* sin_tab, const int* pos,
+    const int* qlens, const int* page_table, int B, int Tq, int NP, int P,
+    int Hq, int Hkv, int D, hipStream_t stream);
 hipError_t tok_attn_decode_ragged_fp8(const void* q, const void* k,
                                       const void* v, const float* kscale,
                                       const float* vscale, const int* lens,
@@ -843,6 +862,144 @@ at::Tensor qkv_rope_append_paged_(at::Tensor qkv, at::Tensor cos_tab,
   return q;
 }
 
+// An e4m3 paged KV cache: code pools [P, Hkv, 64, D], fp32 scale pools
+// [P, Hkv, 64] and a page table [B, NP] int32 on the device.
+void check_paged_fp8(const at::Tensor& kpool, const at::Tensor& vpool,
+                     const at::Tensor& kscale, const at::Tensor& vscale,
+                     const at::Tensor& page_table, long B, long Hkv, long D) {
+  for (const at::Tensor* t : {&kpool, &vpool})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat8_e4m3fn &&
+                    t->is_contiguous() && t->dim() == 4,
+                "fp8 pools must be contiguous float8_e4m3fn GPU tensors "
+                "[P, Hkv, 64, D]");
+  TORCH_CHECK(kpool.sizes() == vpool.sizes() && kpool.size(0) >= 1 &&
+                  kpool.size(1) == Hkv && kpool.size(3) == D,
+              "pools must be [P, Hkv, 64, D]");
+  TORCH_CHECK(kpool.size(2) == 64, "the page size must be 64 tokens, got ",
+              kpool.size(2));
+  TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
+  for (const at::Tensor* t : {&kscale, &vscale})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat &&
+                    t->is_contiguous() && t->dim() == 3 &&
+                    t->size(0) == kpool.size(0) && t->size(1) == Hkv &&
+                    t->size(2) == 64,
+                "kscale and vscale must be contiguous fp32 GPU tensors "
+                "[P, Hkv, 64]");
+  TORCH_CHECK(page_table.is_cuda() && page_table.scalar_type() == at::kInt &&
+                  page_table.is_contiguous() && page_table.dim() == 2 &&
+                  page_table.size(0) == B && page_table.size(1) >= 1,
+              "page_table must be a contiguous int32 GPU tensor [B, NP]");
+  TORCH_CHECK(page_table.size(1) * 64 < (1L << 30) &&
+                  kpool.size(0) < (1L << 31), "pool or table out of range");
+}
+
+void check_i32_rows(const at::Tensor& a, const at::Tensor& b, long B,
+                    const char* what) {
+  for (const at::Tensor* t : {&a, &b})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt &&
+                    t->is_contiguous() && t->numel() == B,
+                what, " must be contiguous int32 GPU tensors of B elements");
+}
+
+// attn_paged over e4m3 pools with one fp32 scale per (page, kv head, slot).
+at::Tensor attn_paged_fp8(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
+                          at::Tensor kscale, at::Tensor vscale,
+                          at::Tensor page_table, at::Tensor lens,
+                          at::Tensor qlens, long num_splits, long chunk) {
+  CHECK_BF16_CUDA(q);
+  TORCH_CHECK(q.dim() == 4 && kpool.dim() == 4,
+              "q [B,Tq,Hq,D], pools [P,Hkv,64,D]");
+  const long B = q.size(0), Tq = q.size(1), Hq = q.size(2), D = q.size(3);
+  const long Hkv = kpool.size(1);
+  TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  const long R = Hq / Hkv;
+  TORCH_CHECK(R == 1 || R == 2 || R == 4 || R == 8,
+              "attn_paged_fp8: Hq/Hkv must be 1, 2, 4 or 8, got ", R);
+  check_paged_fp8(kpool, vpool, kscale, vscale, page_table, B, Hkv, D);
+  const long NP = page_table.size(1), P = kpool.size(0);
+  check_i32_rows(lens, qlens, B, "lens and qlens");
+  const long MT = (Tq * R + 63) / 64;
+  TORCH_CHECK(B >= 1 && B <= 65535 && Tq >= 1 && B * Tq <= 65535 &&
+                  Hkv * MT < (1L << 31) && num_splits >= 1 &&
+                  num_splits <= 1024, "grid out of range");
+  TORCH_CHECK(chunk >= 64 && chunk % 64 == 0 && num_splits * chunk >= 64 * NP,
+              "chunk must be a multiple of 64 and num_splits * chunk must "
+              "cover 64 * NP");
+  auto out = at::empty_like(q);
+  at::Tensor ws;
+  float* wsp = nullptr;
+  if (num_splits > 1) {
+    ws = at::empty({B * Tq * Hq * num_splits * (D + 2)},
+                   q.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  TOK_HIP_OK(tok_attn_paged_fp8(
+      q.data_ptr(), kpool.data_ptr(), vpool.data_ptr(),
+      kscale.data_ptr<float>(), vscale.data_ptr<float>(),
+      page_table.data_ptr<int>(), lens.data_ptr<int>(), qlens.data_ptr<int>(),
+      out.data_ptr(), wsp, (int)B, (int)Tq, (int)NP, (int)P, (int)Hq, (int)Hkv,
+      (int)D, (int)num_splits, (int)chunk, current_stream()));
+  return out;
+}
+
+// k, v: [B, Tq, Hkv, D] bf16 (k already roped). Token i of sequence b is
+// quantized into slot (pos[b] + i) % 64 of page page_table[b, (pos[b] + i) / 64].
+void kv_quantize_append_paged_(at::Tensor k, at::Tensor v, at::Tensor pos,
+                               at::Tensor qlens, at::Tensor kpool,
+                               at::Tensor vpool, at::Tensor kscale,
+                               at::Tensor vscale, at::Tensor page_table) {
+  CHECK_BF16_CUDA(k);
+  CHECK_BF16_CUDA(v);
+  TORCH_CHECK(k.dim() == 4 && k.sizes() == v.sizes(),
+              "k and v must be [B, Tq, Hkv, D]");
+  const long B = k.size(0), Tq = k.size(1), Hkv = k.size(2), D = k.size(3);
+  check_paged_fp8(kpool, vpool, kscale, vscale, page_table, B, Hkv, D);
+  check_i32_rows(pos, qlens, B, "pos and qlens");
+  TORCH_CHECK(B >= 1 && Tq >= 1 && B * Tq < (1L << 31), "B * Tq out of range");
+  TOK_HIP_OK(tok_kv_quantize_append_paged(
+      k.data_ptr(), v.data_ptr(), kpool.data_ptr(), vpool.data_ptr(),
+      kscale.data_ptr<float>(), vscale.data_ptr<float>(),
+      pos.data_ptr<int>(), qlens.data_ptr<int>(), page_table.data_ptr<int>(),
+      (int)B, (int)Tq, (int)page_table.size(1), (int)kpool.size(0), (int)Hkv,
+      (int)D, current_stream()));
+}
+
+// qkv: [B, Tq, (Hq+2Hkv)*D]. Token i of sequence b is rotated at pos[b] + i
+// and its k, v quantized into their page; returns roped bf16 q [B,Tq,Hq,D].
+at::Tensor qkv_rope_append_paged_fp8_(at::Tensor qkv, at::Tensor cos_tab,
+                                      at::Tensor sin_tab, at::Tensor pos,
+                                      at::Tensor qlens, at::Tensor kpool,
+                                      at::Tensor vpool, at::Tensor kscale,
+                                      at::Tensor vscale,
+                                      at::Tensor page_table, long Hq,
+                                      long Hkv, long D) {
+  CHECK_BF16_CUDA(qkv);
+  TORCH_CHECK(cos_tab.is_cuda() && cos_tab.scalar_type() == at::kFloat &&
+              cos_tab.is_contiguous());
+  TORCH_CHECK(sin_tab.is_cuda() && sin_tab.scalar_type() == at::kFloat &&
+              sin_tab.is_contiguous());
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == (Hq + 2 * Hkv) * D,
+              "packed qkv must be [B, Tq, (Hq+2Hkv)*D]");
+  const long B = qkv.size(0), Tq = qkv.size(1);
+  check_paged_fp8(kpool, vpool, kscale, vscale, page_table, B, Hkv, D);
+  const long NP = page_table.size(1), P = kpool.size(0);
+  check_i32_rows(pos, qlens, B, "pos and qlens");
+  TORCH_CHECK(B >= 1 && Tq >= 1 && B * Tq < (1L << 31), "B * Tq out of range");
+  TORCH_CHECK(sin_tab.numel() == cos_tab.numel(), "cos/sin shape mismatch");
+  const long table_rows = cos_tab.numel() / (D / 2);
+  TORCH_CHECK(table_rows >= 64 * NP, "rope table has ", table_rows,
+              " rows, the page table spans ", 64 * NP);
+  auto q = at::empty({B, Tq, Hq, D}, qkv.options());
+  TOK_HIP_OK(tok_qkv_rope_append_paged_fp8(
+      qkv.data_ptr(), q.data_ptr(), kpool.data_ptr(), vpool.data_ptr(),
+      kscale.data_ptr<float>(), vscale.data_ptr<float>(),
+      cos_tab.data_ptr<float>(), sin_tab.data_ptr<float>(),
+      pos.data_ptr<int>(), qlens.data_ptr<int>(), page_table.data_ptr<int>(),
+      (int)B, (int)Tq, (int)NP, (int)P, (int)Hq, (int)Hkv, (int)D,
+      current_stream()));
+  return q;
+}
+
 // An e4m3 KV cache [B,Tmax,Hkv,D] and its fp32 row scales [B,Tmax,Hkv].
 void check_fp8_cache(const at::Tensor& kcache, const at::Tensor& vcache,
                      const at::Tensor& kscale, const at::Tensor& vscale,
@@ -1330,6 +1487,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("num_splits"), py::arg("chunk"));
   mod.def("qkv_rope_append_paged_", &qkv_rope_append_paged_,
           "Multi-token packed-QKV RoPE + paged KV-cache append (bf16, gfx950)");
+  mod.def("attn_paged_fp8", &attn_paged_fp8,
+          "Attention over an e4m3 paged KV cache with per-row scales (gfx950)",
+          py::arg("q"), py::arg("kpool"), py::arg("vpool"), py::arg("kscale"),
+          py::arg("vscale"), py::arg("page_table"), py::arg("lens"),
+          py::arg("qlens"), py::arg("num_splits"), py::arg("chunk"));
+  mod.def("kv_quantize_append_paged_", &kv_quantize_append_paged_,
+          "Quantize roped bf16 K/V rows into an e4m3 paged KV cache (gfx950)");
+  mod.def("qkv_rope_append_paged_fp8_", &qkv_rope_append_paged_fp8_,
+          "Multi-token packed-QKV RoPE + e4m3 paged KV-cache append (gfx950)");
   mod.def("attn_decode_ragged_fp8", &attn_decode_ragged_fp8,
           "Per-sequence-length decode over an e4m3 KV cache with per-row "
           "scales (gfx950)",

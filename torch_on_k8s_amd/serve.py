@@ -30,6 +30,8 @@ Endpoints:
                                   carries the "seed" that was used;
                                   "kv_dtype": "fp8" keeps the KV cache in
                                   e4m3 with per-row scales (ragged only);
+                                  "kv_dtype": "fp8_paged" keeps it in e4m3
+                                  64-token pages, also with "prefill_chunk";
                                   "kv_page_size": 64 keeps the KV cache in
                                   64-token pages (ragged only);
                                   "weight_dtype": "fp8" runs the projections
@@ -253,19 +255,21 @@ def build_app(srv: InferenceServer):
                 400, f"prompt+max_new_tokens exceeds the model's trained "
                      f"context ({max_seq}); RoPE extrapolation beyond it "
                      f"degrades silently")
-        if req.kv_dtype not in (None, "fp8"):
-            raise HTTPException(400, 'kv_dtype must be "fp8" or absent')
+        if req.kv_dtype not in (None, "fp8", "fp8_paged"):
+            raise HTTPException(400, 'kv_dtype must be "fp8", "fp8_paged" '
+                                     'or absent')
         if req.weight_dtype not in (None, "fp8"):
             raise HTTPException(400, 'weight_dtype must be "fp8" or absent')
         if req.kv_page_size not in (None, 64):
             raise HTTPException(400, "kv_page_size must be 64 or absent")
-        if req.kv_page_size is not None and req.kv_dtype is not None:
+        if req.kv_page_size is not None and req.kv_dtype == "fp8":
             raise HTTPException(400, "kv_page_size and kv_dtype do not "
-                                     "combine: the paged pool is bf16")
-        if req.kv_dtype is not None and req.prefill_chunk is not None:
+                                     "combine: the paged pool is bf16 (the "
+                                     'e4m3 pool is "fp8_paged")')
+        if req.kv_dtype == "fp8" and req.prefill_chunk is not None:
             raise HTTPException(400, "kv_dtype and prefill_chunk do not "
                                      "combine: chunked prefill reads a bf16 "
-                                     "cache")
+                                     'cache ("fp8_paged" has one)')
         try:
             return srv.generate(req.prompt_ids, req.max_new_tokens,
                                 temperature=req.temperature, ragged=True,
