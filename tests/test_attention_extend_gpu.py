@@ -2,8 +2,10 @@
 
 Rule: kernel_oracle_attention.compare (|got - ref| <= 2^-8 |ref| + 2^-8 mid
 + k 2^-23 scale + 2^-126), mid = sum_j p_ij |v_j| for P's one bf16 rounding
-(attn_extend.hip, ex_pack in the P repack). The fp32 chains, counted from
-attn_extend.hip as written (one rounding = half a unit), n_t = chunk / 64:
+(attn_extend.hip, kt_pack of attn_kv_tile.h in the P repack). The fp32
+chains, counted from kt_attn and its segments in attn_kv_tile.h as written
+(kt_scores, kt_softmax_step, kt_rescale, kt_pv64, kt_store_*; one rounding =
+half a unit), n_t = chunk / 64:
   score      k_score(D): the D-term MFMA chain of S^T = K Q^T and
              c2 = scale * LOG2E with the fma that applies it (units of sabs)
   exp        K_EXP = 1: one fma and a 1-ulp v_exp_f32; the argument is

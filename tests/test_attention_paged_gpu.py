@@ -3,9 +3,9 @@
 The reference is the plain fp64 masked softmax of test_attention_extend_gpu
 on the logically gathered cache, judged by kernel_oracle_attention.check
 (|got - ref| <= 2^-8 |ref| + 2^-8 mid + k 2^-23 scale + 2^-126, mid =
-sum_j p_ij |v_j| for P's one bf16 rounding, pg_pack in attn_paged.hip). The
-fp32 chains, counted from attn_paged.hip as written (one rounding = half a
-unit), n_t = chunk / 64 tiles per split:
+sum_j p_ij |v_j| for P's one bf16 rounding, kt_pack of attn_kv_tile.h). The
+fp32 chains, counted from attn_paged.hip as written (the same arithmetic as
+kt_attn of attn_kv_tile.h; one rounding = half a unit), n_t = chunk / 64 tiles per split:
   score      k_score(D): the D-term MFMA chain of S^T and c2 with its fma
   exp        K_EXP = 1 per key: one fma and a 1-ulp v_exp_f32. Key-split: 2,
              because the wave fold's weight e_w = exp2((m_w - M) c2) (a
@@ -154,6 +154,29 @@ def test_paged_vs_fp64(Hq, Hkv, D, Tq, S):
                                 pool_of(vc, TABLE2).to(DEV), dev_i32(TABLE2),
                                 lens, qlens, num_splits=S)
     assert torch.equal(moved, out)
+
+
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("S", [1, 2])
+def test_row_layout_is_bit_equal_to_attention_extend(D, S):
+    """Tq * R > 16: over a pool and a shuffled table, attention_paged gives the
+    bits attention_extend gives over the contiguous cache holding the same
+    rows. The two kernels share their arithmetic and differ only in where a
+    tile's bytes come from."""
+    Hq, Hkv, Tq, npages, lens, qlens = 8, 2, 19, 3, [130, 83], [19, 7]
+    g = torch.Generator().manual_seed(7 * D + S)
+    q = ko.q16(torch.randn(2, Tq, Hq, D, generator=g))
+    kc = ko.q16(torch.randn(2, 64 * npages, Hkv, D, generator=g))
+    vc = ko.q16(torch.randn(2, 64 * npages, Hkv, D, generator=g) * 0.5)
+    tab = [[17, 2, 9], [11, 20, P + 5]]   # 83 rows: two pages, one unused
+    n, m = dev_i32(lens), dev_i32(qlens)
+    want = ops.attention_extend(q.to(DEV), kc.to(DEV), vc.to(DEV), n, m,
+                                num_splits=S)
+    got = ops.attention_paged(q.to(DEV), pool_of(kc, tab, lens).to(DEV),
+                              pool_of(vc, tab, lens).to(DEV), dev_i32(tab), n,
+                              m, num_splits=S)
+    assert torch.isfinite(got.float()).all()
+    assert torch.equal(got, want)
 
 
 @pytest.mark.parametrize("Tq", [1, 19])   # key-split, row layout

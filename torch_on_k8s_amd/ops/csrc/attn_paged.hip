@@ -7,61 +7,32 @@
 //     contiguous 64*D*2-byte slab; page_table [B,NP] int32, lens/qlens [B]
 //     int32, all on the device and never read by the host. Logical row t of
 //     sequence b lives in page page_table[b, t / 64], slot t % 64.
-//     Tmax = 64 NP, n = clamp(lens[b], 0, Tmax), m = clamp(qlens[b], 0,
-//     min(Tq, n)); query i < m sits at p_i = n - m + i and attends to rows
-//     [0, p_i]; rows i >= m are exactly zero and read nothing. A page id is
-//     clamped into [0, P): a wrong table gives wrong numbers, never a fault.
+//     Tmax = 64 NP. A page id is clamped into [0, P): a wrong table gives
+//     wrong numbers, never a fault.
+//     The design written up in attn_kv_tile.h (work split, both layouts,
+//     operand layouts, LDS image, bank argument, softmax, fold, epilogue);
+//     the launcher picks the key-split layout for Tq * R <= 16. The body is
+//     NOT yet an instance of kt_attn: as one it computed the same bits but
+//     ran 3-5 % slower than this text on the bandwidth-bound row-layout
+//     lines (Tq = 8, equal lengths, T = 32768; profiles/README.md), so it
+//     stays as it was, on the shared primitives, until that is understood.
 //
 // Staging. A key tile IS a page. The id of tile t + 2 is read from the table
 // one iteration ahead (a uniform scalar load whose wait falls on the next
-// iteration's first LDS wait), clamped, and turned into the two slab bases;
-// the K and the V slab go global -> LDS by 16-byte DMA (ex_glds16 of
-// attn_extend.hip, the inline-asm form: the builtin forces vmcnt(0)), two
-// buffers: tile t+1 is issued, vmcnt(NDMA) says tile t has landed in this
-// wave, a barrier says so of every wave, a second barrier after the MFMAs
-// frees the buffer. The source slot is min(slot, last valid slot of the
-// tile): 63 everywhere but in the tile that holds row kend - 1, so a row
-// >= n of a tail page (NaN from an earlier owner) never enters LDS. A slab is
-// contiguous, so the DMA offset is slot * D*2 + chunk * 16 and needs no row
-// stride. The LDS image, the XOR swizzle f on the source chunk and on the
-// read address, and the bank argument are those of attn_extend.hip; what
-// changes for the key-split reads: a wave reads K rows 16w + 0..15 (one
-// chunk) and V rows 16w + 4g + q instead of 16kt + .. and 16u + ..; f takes
-// r & 15 only, so both reads hit the same sixteen distinct slots.
-//
-// Row layout (KEYSPLIT = false, Tq * R > 16): the work split and products of
-// attn_extend_kernel. Four waves x 16 packed rows (token, head of group),
-// S^T = K Q^T with mfma_f32_16x16x32_bf16, the accumulator is the A operand
-// of P V, V by ds_read_b64_tr_b16, online softmax in the log2 domain.
-//
-// Key-split layout (KEYSPLIT = true, Tq * R <= 16; decode is Tq = 1): one
-// 16-row tile of packed rows for the block; wave w owns keys 16w .. 16w + 15
-// of every page. Per tile a wave runs one KS-step S^T chain (A = K rows
-// 16w + i, B = Q resident) and P V on its 16 keys with
-// mfma_f32_16x16x16_bf16: lane (i, g) of the S^T accumulator holds q row i,
-// keys 4g .. 4g + 3, which is that instruction's A operand (row i, k-slots
-// 4g .. 4g + 3); one transposed b64 read hands lane (i, g) column 16dt + i of
-// V rows 16w + 4g .. + 3, its B operand. Each wave keeps its own (m, l, o[D])
-// for the 16 rows over all tiles of the split; at the end the four states go
-// to LDS as fp32 and 16 * D/8 threads fold them in wave order:
-// M = max m_w, e_w = exp2((m_w - M) c2), L = fma(l_w, e_w, L),
-// o = fma(o_w, e_w, o). No atomics, fixed order. A wave's mask test uses its
-// own 16 keys against the row limits; a wave whose keys all lie past the last
-// row's limit skips the tile's arithmetic. Dead rows run with q = 0 and are
-// zeroed by select.
-//
-// Epilogue: one split writes bf16 rows as 16-byte stores (row layout: through
-// an LDS image; key-split: straight from the fold); more than one split
-// writes fp32 (m, l, o[D]) partials in the workspace layout of
-// attn_decode_ragged_combine, folded by tok_attn_ragged_combine.
+// iteration's first LDS wait), clamped, and turned into the two slab bases.
+// The source slot is min(slot, last valid slot of the tile): 63 everywhere
+// but in the tile that holds row kend - 1, so a row >= n of a tail page (NaN
+// from an earlier owner) never enters LDS. A slab is contiguous, so the DMA
+// offset is slot * D*2 + chunk * 16 and needs no row stride.
 //
 //   qkv_rope_append_paged_kernel   grid-stride, 256 threads
 //     qkv_rope_append_chunk_kernel with the destination looked up in the
-//     table; per element the same arithmetic, so the same bytes for the same
-//     token. Token i of sequence b is live iff i < qlens[b],
-//     0 <= pos[b] + i < 64 NP and its table entry is in [0, P); a dead token
-//     writes nothing (a clamped write would land in someone else's page) and
-//     gets a zero q row.
+//     table (the rule of KtPagedDest, attn_kv_tile.h; see attn_extend.hip
+//     for why the body is not shared); per element the same arithmetic.
+//     Token i of sequence b is live iff i < qlens[b],
+//     0 <= pos[b] + i < 64 NP and its table entry is in [0, P);
+//     a dead token writes nothing (a clamped write would land in someone
+//     else's page) and gets a zero q row.
 //
 // Resources (hipcc -O3 --offload-arch=gfx950,
 // -Rpass-analysis=kernel-resource-usage; scratch is 0 B everywhere):
@@ -80,7 +51,7 @@
 // vmcnt(0); the table reads are s_load_dword. The compiler's own wait for the
 // q loads would be a vmcnt(0) inside the loop (it does not count the
 // inline-asm DMAs), so q is "used" by an empty asm before the loop.
-#include "common.h"
+#include "attn_kv_tile.h"
 
 extern "C" hipError_t tok_attn_ragged_combine(const float* ws, void* out,
                                               int rows, int Hq, int D,
@@ -89,77 +60,6 @@ extern "C" hipError_t tok_attn_ragged_combine(const float* ws, void* out,
 
 namespace {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PG_KERNEL __global__ __attribute__((target("no-packed-fp32-ops")))
-#else
-#define PG_KERNEL __global__
-#endif
-
-using bf16x8v = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x2v = __attribute__((ext_vector_type(2))) __bf16;
-using i16x4v = __attribute__((ext_vector_type(4))) short;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-
-constexpr int PG_NTH = 256;
-constexpr int PG_PAGE = 64;  // tokens per page = keys per tile
-constexpr float PG_LOG2E = 1.4426950408889634f;
-
-typedef __attribute__((address_space(3))) i16x4v* pg_tr_ptr;
-
-DEVINL i16x4v pg_tr_read(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((pg_tr_ptr)p);
-}
-
-// 16 bytes per lane, global -> LDS: lane i's bytes land at lds_dst + 16 i.
-DEVINL void pg_glds16(uint32_t voff, const void* sbase, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
-
-DEVINL void pg_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int D>
-DEVINL int pg_swz(int r) {
-  if (D == 128)
-    return ((r & 3) << 2) | (((r >> 2) & 1) << 1) | ((r >> 3) & 1);
-  return (((r >> 1) & 1) << 2) | (((r >> 2) & 1) << 1) | ((r >> 3) & 1);
-}
-
-DEVINL uint32_t pg_pack(float lo, float hi) {
-  const f32x2 f = {lo, hi};
-  union { bf16x2v b; uint32_t u; } c;
-  c.b = __builtin_convertvector(f, bf16x2v);
-  return c.u;
-}
-
-// packed row (token i, head r of the group) = i*R + r -> index in [B*Tq*Hq]
-template <int R>
-struct PgRows {
-  long tok0;   // b * Tq
-  int Hq, h0;  // h0 = hkv * R
-  DEVINL long global(int row) const {
-    return (tok0 + row / R) * Hq + h0 + row % R;
-  }
-};
-
-// A wave-uniform pointer, pinned to SGPRs for the DMA's scalar base.
-DEVINL const char* pg_uniform(const char* p) {
-  const uint64_t a = (uint64_t)(uintptr_t)p;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-  return (const char*)(uintptr_t)(((uint64_t)hi << 32) | lo);
-}
-
 // The K and the V slab of page raw_id (clamped into [0, P): never a fault)
 // of the kv head at head_off, slots clamped to last_slot, into the pair of
 // tiles at LDS address dst (wave part included).
@@ -167,28 +67,28 @@ template <int D>
 DEVINL void pg_stage(const char* kpool, const char* vpool, int raw_id, int P,
                      long page_bytes, long head_off, uint32_t dst,
                      int last_slot, int d_row, int d_ch) {
-  constexpr int TILE = PG_PAGE * D * 2, NJ = TILE / 4096, RPS = 4096 / (D * 2);
+  constexpr int TILE = KT_PAGE * D * 2, NJ = TILE / 4096, RPS = 4096 / (D * 2);
   const long slab = min(max(raw_id, 0), P - 1) * page_bytes + head_off;
-  const char* kb = pg_uniform(kpool + slab);
-  const char* vb = pg_uniform(vpool + slab);
+  const char* kb = kt_uniform(kpool + slab);
+  const char* vb = kt_uniform(vpool + slab);
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int slot = min(j * RPS + d_row, last_slot);
     const uint32_t voff = (uint32_t)slot * (D * 2) + d_ch * 16;
-    pg_glds16(voff, kb, dst + j * 4096);
-    pg_glds16(voff, vb, dst + TILE + j * 4096);
+    kt_glds16(voff, kb, dst + j * 4096);
+    kt_glds16(voff, vb, dst + TILE + j * 4096);
   }
 }
 
 template <int D, int R, bool KEYSPLIT>
-PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
+KT_KERNEL __launch_bounds__(KT_NTH, 2) void attn_paged_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ kpool,
     const bf16_t* __restrict__ vpool, const int* __restrict__ page_table,
     const int* __restrict__ lens, const int* __restrict__ qlens,
     bf16_t* __restrict__ out, float* __restrict__ ws, int Tq, int NP, int P,
     int Hkv, int MT, int chunk, float scale) {
   constexpr int RB = D * 2;                    // bytes per tile row
-  constexpr int TILE = PG_PAGE * RB;           // one K or V slab
+  constexpr int TILE = KT_PAGE * RB;           // one K or V slab
   constexpr int NJ = TILE / 4096;              // DMA instructions per slab
   constexpr int CPR = D / 8;                   // 16-byte chunks per row
   constexpr int KS = D / 32;                   // k steps of S^T
@@ -210,7 +110,7 @@ PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
   const int S = gridDim.z;
   const int Hq = Hkv * R;
   const int NR = Tq * R;                       // packed rows of this kv head
-  const int Tmax = NP * PG_PAGE;
+  const int Tmax = NP * KT_PAGE;
 
   const int n = min(max(lens[b], 0), Tmax);
   const int m = min(max(qlens[b], 0), min(Tq, n));
@@ -223,11 +123,11 @@ PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
   const int kbeg = sp * chunk;
   const int kend = min(kbeg + chunk, p_last + 1);
 
-  const PgRows<R> rows{(long)b * Tq, Hq, hkv * R};
+  const KtRows<R> rows{(long)b * Tq, Hq, hkv * R};
   const long ws_ml0 = (long)gridDim.y * Tq * Hq * S * D;
 
   if (i_first >= m || kbeg >= kend) {  // block-uniform: nothing to attend to
-    for (int idx = tid; idx < BM * CPR; idx += PG_NTH) {
+    for (int idx = tid; idx < BM * CPR; idx += KT_NTH) {
       const int row = row_blk + idx / CPR, ch = idx % CPR;
       if (row >= NR) continue;
       const long gr = rows.global(row);
@@ -279,12 +179,12 @@ PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
       (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem +
       wid * 1024);
   const int d_row = tid / CPR;                         // slot within a 4 KiB
-  const int d_ch = (tid % CPR) ^ pg_swz<D>(d_row & 15);
+  const int d_ch = (tid % CPR) ^ kt_swz<D>(d_row & 15);
   const char* kbytes = reinterpret_cast<const char*>(kpool);
   const char* vbytes = reinterpret_cast<const char*>(vpool);
   const int* tab = page_table + (long)b * NP;
-  const int pg0 = kbeg / PG_PAGE;                      // < NP: kbeg < kend <= n
-  const int ntiles = (kend - kbeg + PG_PAGE - 1) / PG_PAGE;
+  const int pg0 = kbeg / KT_PAGE;                      // < NP: kbeg < kend <= n
+  const int ntiles = (kend - kbeg + KT_PAGE - 1) / KT_PAGE;
   const long head_off = (long)hkv * TILE;
   const int krem = kend - 1 - kbeg;                    // last row, from kbeg
 
@@ -292,7 +192,7 @@ PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
   uint32_t k_off[KS];   // + kt * 16 * RB
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
-    k_off[ks] = li * RB + 16 * ((4 * ks + lg) ^ pg_swz<D>(li));
+    k_off[ks] = li * RB + 16 * ((4 * ks + lg) ^ kt_swz<D>(li));
   // transposed read: lane 4q+p of group g supplies row 16u + 4g + q, columns
   // 16dt + 4p .. + 3: chunk 2dt + (p >> 1), half p & 1. Row layout: u = 0, 1
   // (+ 32kk); key-split: u = w only.
@@ -303,11 +203,11 @@ PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
     for (int u = 0; u < 2; ++u) {
       const int r = 16 * (KEYSPLIT ? wid : u) + 4 * lg + tq;
       v_base[u] = r * RB + 8 * (tp & 1);
-      v_x[u] = (tp >> 1) ^ pg_swz<D>(r & 15);
+      v_x[u] = (tp >> 1) ^ kt_swz<D>(r & 15);
     }
   }
 
-  const float c2 = scale * PG_LOG2E;
+  const float c2 = scale * KT_LOG2E;
   float m_run = -INFINITY, l_run = 0.f;
   f32x4 o_acc[DT];
 #pragma unroll
@@ -315,7 +215,7 @@ PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
 
   const long page_bytes = (long)Hkv * TILE;
   pg_stage<D>(kbytes, vbytes, tab[pg0], P, page_bytes, head_off, lds0,
-              min(PG_PAGE - 1, krem), d_row, d_ch);
+              min(KT_PAGE - 1, krem), d_row, d_ch);
   int id_next = tab[pg0 + min(1, ntiles - 1)];         // raw id of tile t + 1
   // Use q here, so that the compiler's wait for the q loads sits before the
   // loop (tile 0 must land anyway) and not as a vmcnt(0) inside it.
@@ -325,16 +225,16 @@ PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
     const int buf = t & 1;
     pg_stage<D>(kbytes, vbytes, id_next, P, page_bytes, head_off,
                 lds0 + (buf ^ 1) * 2 * TILE,
-                min(PG_PAGE - 1, krem - min(t + 1, ntiles - 1) * PG_PAGE),
+                min(KT_PAGE - 1, krem - min(t + 1, ntiles - 1) * KT_PAGE),
                 d_row, d_ch);
     id_next = tab[pg0 + min(t + 2, ntiles - 1)];
     if (NJ == 4)
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    pg_barrier();
+    kt_barrier();
 
-    const int k0 = kbeg + t * PG_PAGE;
+    const int k0 = kbeg + t * KT_PAGE;
     const int kw0 = k0 + 16 * kt0;                     // wave's first key
     if (wave_live && kw0 <= lim_last) {
       const char* kt_lds = smem + buf * 2 * TILE + kt0 * 16 * RB;
@@ -406,12 +306,12 @@ PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
       if constexpr (KEYSPLIT) {
         // P of the wave's 16 keys IS the A operand of the K = 16 MFMA
         union { uint32_t w[2]; i16x4v f; } pa;
-        pa.w[0] = pg_pack(st[0][0], st[0][1]);
-        pa.w[1] = pg_pack(st[0][2], st[0][3]);
+        pa.w[0] = kt_pack(st[0][0], st[0][1]);
+        pa.w[1] = kt_pack(st[0][2], st[0][3]);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
           const i16x4v vb =
-              pg_tr_read(vt_lds + v_base[0] + 16 * ((2 * dt) ^ v_x[0]));
+              kt_tr_read(vt_lds + v_base[0] + 16 * ((2 * dt) ^ v_x[0]));
           o_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(
               pa.f, vb, o_acc[dt], 0, 0, 0);
         }
@@ -421,10 +321,10 @@ PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
           union { uint32_t w[4]; bf16x8v f; } c;
-          c.w[0] = pg_pack(st[2 * kk][0], st[2 * kk][1]);
-          c.w[1] = pg_pack(st[2 * kk][2], st[2 * kk][3]);
-          c.w[2] = pg_pack(st[2 * kk + 1][0], st[2 * kk + 1][1]);
-          c.w[3] = pg_pack(st[2 * kk + 1][2], st[2 * kk + 1][3]);
+          c.w[0] = kt_pack(st[2 * kk][0], st[2 * kk][1]);
+          c.w[1] = kt_pack(st[2 * kk][2], st[2 * kk][3]);
+          c.w[2] = kt_pack(st[2 * kk + 1][0], st[2 * kk + 1][1]);
+          c.w[3] = kt_pack(st[2 * kk + 1][2], st[2 * kk + 1][3]);
           pa[kk] = c.f;
         }
 #pragma unroll
@@ -434,17 +334,17 @@ PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
             union { i16x4v s[2]; bf16x8v f; } vb;
 #pragma unroll
             for (int u = 0; u < 2; ++u)
-              vb.s[u] = pg_tr_read(vt_lds + kk * 32 * RB + v_base[u] +
+              vb.s[u] = kt_tr_read(vt_lds + kk * 32 * RB + v_base[u] +
                                    16 * ((2 * dt) ^ v_x[u]));
             o_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                 pa[kk], vb.f, o_acc[dt], 0, 0, 0);
           }
       }
     }
-    pg_barrier();
+    kt_barrier();
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  pg_barrier();
+  kt_barrier();
 
   // ---- row sums: the four lanes of a row, in g order ----
   float l_row = 0.f;
@@ -559,11 +459,9 @@ PG_KERNEL __launch_bounds__(PG_NTH, 2) void attn_paged_kernel(
   }
 }
 
-constexpr int BLOCK_APPP = 256;
-
 // Work item = one 8-wide vec of the first half of one head row of one token
 // and its partner in the second half, as qkv_rope_append_chunk_kernel.
-PG_KERNEL void qkv_rope_append_paged_kernel(
+KT_KERNEL void qkv_rope_append_paged_kernel(
     const bf16x8* __restrict__ qkv, bf16x8* __restrict__ q,
     bf16x8* __restrict__ kpool, bf16x8* __restrict__ vpool,
     const float* __restrict__ tab_cos, const float* __restrict__ tab_sin,
@@ -573,8 +471,8 @@ PG_KERNEL void qkv_rope_append_paged_kernel(
   const int heads_total = Hq + 2 * Hkv;
   const int dv8 = hv * 2;  // vecs per head (D/8)
   const long nwork = (long)B * Tq * heads_total * hv;
-  for (long i = (long)blockIdx.x * BLOCK_APPP + threadIdx.x; i < nwork;
-       i += (long)gridDim.x * BLOCK_APPP) {
+  for (long i = (long)blockIdx.x * KT_NTH + threadIdx.x; i < nwork;
+       i += (long)gridDim.x * KT_NTH) {
     const long rowh = i / hv;                 // (b*Tq + t)*heads_total + h
     const int c = (int)(i - rowh * hv);
     const long tok = rowh / heads_total;      // b*Tq + t
@@ -582,10 +480,10 @@ PG_KERNEL void qkv_rope_append_paged_kernel(
     const int b = (int)(tok / Tq);
     const int t = (int)(tok - (long)b * Tq);
     const long p = (long)pos[b] + t;
-    bool live = t < qlens[b] && p >= 0 && p < (long)NP * PG_PAGE;
+    bool live = t < qlens[b] && p >= 0 && p < (long)NP * KT_PAGE;
     int pid = -1;
     if (live) {  // the table is read only at an index inside it
-      pid = page_table[(long)b * NP + p / PG_PAGE];
+      pid = page_table[(long)b * NP + p / KT_PAGE];
       live = pid >= 0 && pid < P;
     }
     bf16x8* dst;
@@ -606,7 +504,7 @@ PG_KERNEL void qkv_rope_append_paged_kernel(
       const bool isk = h < Hq + Hkv;
       const int hh = isk ? h - Hq : h - Hq - Hkv;
       dst = (isk ? kpool : vpool) +
-            (((long)pid * Hkv + hh) * PG_PAGE + (p % PG_PAGE)) * dv8;
+            (((long)pid * Hkv + hh) * KT_PAGE + (p % KT_PAGE)) * dv8;
       rot = isk;
     }
     const bf16x8* src = qkv + rowh * dv8;
@@ -634,46 +532,6 @@ PG_KERNEL void qkv_rope_append_paged_kernel(
   }
 }
 
-struct PgArgs {
-  const void *q, *k, *v;
-  const int *table, *lens, *qlens;
-  void* out;
-  float* ws;
-  int B, Tq, NP, P, Hkv, num_splits, chunk;
-  hipStream_t stream;
-};
-
-// The layout is picked here: up to 16 packed rows run key-split.
-template <int D, int R>
-void launch_paged(const PgArgs& a) {
-  const float scale = 1.f / sqrtf((float)D);
-  if (a.Tq * R <= 16) {
-    dim3 grid(a.Hkv, a.B, a.num_splits);
-    attn_paged_kernel<D, R, true><<<grid, PG_NTH, 0, a.stream>>>(
-        (const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, a.table,
-        a.lens, a.qlens, (bf16_t*)a.out, a.ws, a.Tq, a.NP, a.P, a.Hkv, 1,
-        a.chunk, scale);
-  } else {
-    const int MT = (a.Tq * R + 63) / 64;
-    dim3 grid(a.Hkv * MT, a.B, a.num_splits);
-    attn_paged_kernel<D, R, false><<<grid, PG_NTH, 0, a.stream>>>(
-        (const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v, a.table,
-        a.lens, a.qlens, (bf16_t*)a.out, a.ws, a.Tq, a.NP, a.P, a.Hkv, MT,
-        a.chunk, scale);
-  }
-}
-
-template <int D>
-bool launch_paged_r(int R, const PgArgs& a) {
-  switch (R) {
-    case 1: launch_paged<D, 1>(a); return true;
-    case 2: launch_paged<D, 2>(a); return true;
-    case 4: launch_paged<D, 4>(a); return true;
-    case 8: launch_paged<D, 8>(a); return true;
-    default: return false;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -685,18 +543,29 @@ hipError_t tok_attn_paged(const void* q, const void* kpool, const void* vpool,
                           int Tq, int NP, int P, int Hq, int Hkv, int D,
                           int num_splits, int chunk, hipStream_t stream) {
   if (Hkv < 1 || Hq % Hkv != 0 || Tq < 1 || B < 1 || NP < 1 || P < 1 ||
-      num_splits < 1 || chunk < PG_PAGE || chunk % PG_PAGE != 0 ||
-      (long)num_splits * chunk < (long)NP * PG_PAGE ||
-      (long)NP * PG_PAGE >= (1L << 30))
+      num_splits < 1 || chunk < KT_PAGE || chunk % KT_PAGE != 0 ||
+      (long)num_splits * chunk < (long)NP * KT_PAGE ||
+      (long)NP * KT_PAGE >= (1L << 30))
     return hipErrorInvalidValue;
-  const PgArgs a{q, kpool, vpool, page_table, lens, qlens, out, ws, B, Tq,
-                 NP, P, Hkv, num_splits, chunk, stream};
-  const int R = Hq / Hkv;
-  bool ok = false;
-  if (D == 128)
-    ok = launch_paged_r<128>(R, a);
-  else if (D == 64)
-    ok = launch_paged_r<64>(R, a);
+  const bool ok = kt_dispatch(D, Hq / Hkv, [&](auto d, auto r) {
+    constexpr int DD = decltype(d)::value, R = decltype(r)::value;
+    const float scale = 1.f / sqrtf((float)DD);
+    // The layout is picked here: up to 16 packed rows run key-split.
+    if (Tq * R <= 16) {
+      dim3 grid(Hkv, B, num_splits);
+      attn_paged_kernel<DD, R, true><<<grid, KT_NTH, 0, stream>>>(
+          (const bf16_t*)q, (const bf16_t*)kpool, (const bf16_t*)vpool,
+          page_table, lens, qlens, (bf16_t*)out, ws, Tq, NP, P, Hkv, 1, chunk,
+          scale);
+    } else {
+      const int MT = (Tq * R + 63) / 64;
+      dim3 grid(Hkv * MT, B, num_splits);
+      attn_paged_kernel<DD, R, false><<<grid, KT_NTH, 0, stream>>>(
+          (const bf16_t*)q, (const bf16_t*)kpool, (const bf16_t*)vpool,
+          page_table, lens, qlens, (bf16_t*)out, ws, Tq, NP, P, Hkv, MT, chunk,
+          scale);
+    }
+  });
   if (!ok) return hipErrorInvalidValue;
   HIP_CHECK(hipGetLastError());
   if (num_splits > 1)
@@ -712,11 +581,8 @@ hipError_t tok_qkv_rope_append_paged(const void* qkv, void* q, void* kpool,
                                      int B, int Tq, int NP, int P, int Hq,
                                      int Hkv, int D, hipStream_t stream) {
   const int hv = (D / 2) / 8;
-  const long nwork = (long)B * Tq * (Hq + 2 * Hkv) * hv;
-  long grid = (nwork + BLOCK_APPP - 1) / BLOCK_APPP;
-  if (grid > 8192) grid = 8192;
-  if (grid < 1) grid = 1;
-  qkv_rope_append_paged_kernel<<<(int)grid, BLOCK_APPP, 0, stream>>>(
+  const int grid = kt_append_grid((long)B * Tq * (Hq + 2 * Hkv) * hv);
+  qkv_rope_append_paged_kernel<<<grid, KT_NTH, 0, stream>>>(
       (const bf16x8*)qkv, (bf16x8*)q, (bf16x8*)kpool, (bf16x8*)vpool, cos_tab,
       sin_tab, pos, qlens, page_table, B, Tq, NP, P, Hq, Hkv, hv);
   return hipGetLastError();

@@ -1,5 +1,6 @@
 // FP8 (OCP e4m3) KV cache for ragged decode on MI355X (gfx950): the decode
-// kernel that reads it and the two kernels that write it.
+// kernel that reads it, the two kernels that write it, and the paged forms
+// of those two.
 //
 // Format. kcache/vcache [B,Tmax,Hkv,D] e4m3 codes (max 448, no infinities,
 // 0x7F / 0xFF are NaN), kscale/vscale [B,Tmax,Hkv] fp32; a stored element
@@ -67,6 +68,15 @@
 //     bf16 row is quantized; a v row is quantized as it is. amax over the
 //     D/16 consecutive lanes of a row by shuffle.
 //
+//   qkv_rope_append_paged_fp8_kernel / kv_quantize_append_paged_kernel
+//     The two kernels above for the paged cache of attn_paged_fp8.hip
+//     (kpool/vpool [P,Hkv,64,D] codes, kscale/vscale [P,Hkv,64]), with the
+//     destination looked up in the table (KtPagedDest, attn_kv_tile.h) as
+//     qkv_rope_append_paged_kernel does: the same quantizer per element, so
+//     the same codes and scale for the same token. A token is dead if
+//     i >= qlens[b], its position is outside [0, 64 NP) or its table entry is
+//     outside [0, P); it writes neither codes nor scale and gets a zero q row.
+//
 // Resources (hipcc -O3 --offload-arch=gfx950,
 // -Rpass-analysis=kernel-resource-usage; scratch is 0 B everywhere):
 //   kernel                                 VGPR  AGPR  SGPR  LDS B  waves/SIMD
@@ -78,11 +88,13 @@
 //   attn_decode_ragged_fp8_kernel<64,2>      111     0    40   2112  4
 //   attn_decode_ragged_fp8_kernel<64,4>      160     0    39   4224  3
 //   attn_decode_ragged_fp8_kernel<64,8>      256     4    46   8448  1
-//   kv_quantize_append_kernel<16|8>        33|32     0    56      0  8
+//   kv_quantize_append_kernel<16|8>        28|26     0    56      0  8
 //   qkv_rope_append_fp8_kernel<8|4>           61     0    60      0  8
+//   qkv_rope_append_paged_fp8_kernel<8|4>     60     0    64      0  8
+//   kv_quantize_append_paged_kernel<16|8>  28|26     0    60      0  8
 // (R = 8 keeps 4 values in AGPRs, not in scratch, and runs one wave per
 // SIMD where the bf16 kernel runs two.)
-#include "common.h"
+#include "attn_kv_tile.h"
 
 extern "C" hipError_t tok_attn_ragged_combine(const float* ws, void* out,
                                               int rows, int Hq, int D,
@@ -90,14 +102,6 @@ extern "C" hipError_t tok_attn_ragged_combine(const float* ws, void* out,
                                               hipStream_t stream);
 
 namespace {
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define F8_KERNEL __global__ __attribute__((target("no-packed-fp32-ops")))
-#else
-#define F8_KERNEL __global__
-#endif
-
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 
 constexpr int NW_F8 = 4;
 constexpr int NTH_F8 = NW_F8 * WAVE;  // 256
@@ -174,7 +178,7 @@ DEVINL float f8_exp_diff(float a, float b) {
 }
 
 template <int D, int R>
-F8_KERNEL __launch_bounds__(NTH_F8) void attn_decode_ragged_fp8_kernel(
+KT_KERNEL __launch_bounds__(NTH_F8) void attn_decode_ragged_fp8_kernel(
     const bf16_t* __restrict__ q, const uint8_t* __restrict__ k,
     const uint8_t* __restrict__ v, const float* __restrict__ kscale,
     const float* __restrict__ vscale, const int* __restrict__ lens,
@@ -378,8 +382,6 @@ F8_KERNEL __launch_bounds__(NTH_F8) void attn_decode_ragged_fp8_kernel(
   }
 }
 
-constexpr int BLOCK_Q8 = 256;
-
 // scale and 1/scale of a row from its amax (0, 0 for an all-zero row)
 DEVINL void f8_row_scale(float amax, float* scale, float* inv) {
   const float s = amax / F8_MAX;
@@ -388,18 +390,19 @@ DEVINL void f8_row_scale(float amax, float* scale, float* inv) {
 }
 
 // Work item = 8 elements of one head row of k (which = 0) or v (which = 1).
-template <int LPR>
-F8_KERNEL void kv_quantize_append_kernel(
+// Dest (attn_kv_tile.h) says where a token's row goes, or that it is dead.
+template <int LPR, class Dest>
+DEVINL void f8_quantize_append(
     const bf16x8* __restrict__ k, const bf16x8* __restrict__ v,
     uint2* __restrict__ kcache, uint2* __restrict__ vcache,
     float* __restrict__ kscale, float* __restrict__ vscale,
-    const int* __restrict__ pos, const int* __restrict__ qlens, int B, int Tq,
-    int Tmax, int Hkv) {
+    const int* __restrict__ pos, const int* __restrict__ qlens,
+    const Dest& dest, int B, int Tq, int Hkv) {
   // nwork is a multiple of LPR and LPR divides the block: the lanes of a row
   // enter and leave the loop together
   const long nwork = (long)B * Tq * 2 * Hkv * LPR;
-  for (long i = (long)blockIdx.x * BLOCK_Q8 + threadIdx.x; i < nwork;
-       i += (long)gridDim.x * BLOCK_Q8) {
+  for (long i = (long)blockIdx.x * KT_NTH + threadIdx.x; i < nwork;
+       i += (long)gridDim.x * KT_NTH) {
     const long row = i / LPR;                   // (tok*2 + which)*Hkv + h
     const int c = (int)(i - row * LPR);
     const long tw = row / Hkv;                  // tok*2 + which
@@ -408,8 +411,7 @@ F8_KERNEL void kv_quantize_append_kernel(
     const bool isv = tw & 1;
     const int b = (int)(tok / Tq);
     const int t = (int)(tok - (long)b * Tq);
-    const long p = (long)pos[b] + t;
-    const bool live = t < qlens[b] && p >= 0 && p < Tmax;
+    const long dst = dest.row(b, (long)pos[b] + t, t < qlens[b], h);
     float x[8];
     f8_unpack_bf8((isv ? v : k)[(tok * Hkv + h) * LPR + c], x);
     const float amax = f8_group_max<LPR>(f8_amax8(x));
@@ -417,18 +419,40 @@ F8_KERNEL void kv_quantize_append_kernel(
     f8_row_scale(amax, &scale, &inv);
     uint2 codes = f8_pack8(x, inv);
     if (!(amax > 0.f)) codes = make_uint2(0u, 0u);
-    if (live) {
-      const long dst = ((long)b * Tmax + p) * Hkv + h;
+    if (dst >= 0) {
       (isv ? vcache : kcache)[dst * LPR + c] = codes;
       if (c == 0) (isv ? vscale : kscale)[dst] = scale;
     }
   }
 }
 
+template <int LPR>
+KT_KERNEL void kv_quantize_append_kernel(
+    const bf16x8* __restrict__ k, const bf16x8* __restrict__ v,
+    uint2* __restrict__ kcache, uint2* __restrict__ vcache,
+    float* __restrict__ kscale, float* __restrict__ vscale,
+    const int* __restrict__ pos, const int* __restrict__ qlens, int B, int Tq,
+    int Tmax, int Hkv) {
+  f8_quantize_append<LPR>(k, v, kcache, vcache, kscale, vscale, pos, qlens,
+                          KtContigDest{Tmax, Hkv}, B, Tq, Hkv);
+}
+
+template <int LPR>
+KT_KERNEL void kv_quantize_append_paged_kernel(
+    const bf16x8* __restrict__ k, const bf16x8* __restrict__ v,
+    uint2* __restrict__ kpool, uint2* __restrict__ vpool,
+    float* __restrict__ kscale, float* __restrict__ vscale,
+    const int* __restrict__ pos, const int* __restrict__ qlens,
+    const int* __restrict__ page_table, int B, int Tq, int NP, int P,
+    int Hkv) {
+  f8_quantize_append<LPR>(k, v, kpool, vpool, kscale, vscale, pos, qlens,
+                          KtPagedDest{page_table, NP, P, Hkv}, B, Tq, Hkv);
+}
+
 // Work item = one 8-wide vec of the first half of one head row of one token
 // and its partner in the second half, as qkv_rope_append_chunk_kernel.
 template <int HV /* (D/2)/8 */>
-F8_KERNEL void qkv_rope_append_fp8_kernel(
+KT_KERNEL void qkv_rope_append_fp8_kernel(
     const bf16x8* __restrict__ qkv, bf16x8* __restrict__ q,
     uint2* __restrict__ kcache, uint2* __restrict__ vcache,
     float* __restrict__ kscale, float* __restrict__ vscale,
@@ -439,8 +463,8 @@ F8_KERNEL void qkv_rope_append_fp8_kernel(
   const int heads_total = Hq + 2 * Hkv;
   constexpr int dv8 = hv * 2;  // vecs per head (D/8)
   const long nwork = (long)B * Tq * heads_total * hv;
-  for (long i = (long)blockIdx.x * BLOCK_Q8 + threadIdx.x; i < nwork;
-       i += (long)gridDim.x * BLOCK_Q8) {
+  for (long i = (long)blockIdx.x * KT_NTH + threadIdx.x; i < nwork;
+       i += (long)gridDim.x * KT_NTH) {
     const long rowh = i / hv;                 // (b*Tq + t)*heads_total + h
     const int c = (int)(i - rowh * hv);
     const long tok = rowh / heads_total;      // b*Tq + t
@@ -505,6 +529,86 @@ F8_KERNEL void qkv_rope_append_fp8_kernel(
   }
 }
 
+// Work item = one 8-wide vec of the first half of one head row of one token
+// and its partner in the second half, as qkv_rope_append_fp8_kernel.
+template <int HV /* (D/2)/8 */>
+KT_KERNEL void qkv_rope_append_paged_fp8_kernel(
+    const bf16x8* __restrict__ qkv, bf16x8* __restrict__ q,
+    uint2* __restrict__ kpool, uint2* __restrict__ vpool,
+    float* __restrict__ kscale, float* __restrict__ vscale,
+    const float* __restrict__ tab_cos, const float* __restrict__ tab_sin,
+    const int* __restrict__ pos, const int* __restrict__ qlens,
+    const int* __restrict__ page_table, int B, int Tq, int NP, int P, int Hq,
+    int Hkv) {
+  constexpr int hv = HV;
+  const int heads_total = Hq + 2 * Hkv;
+  constexpr int dv8 = hv * 2;  // vecs per head (D/8)
+  const long nwork = (long)B * Tq * heads_total * hv;
+  for (long i = (long)blockIdx.x * KT_NTH + threadIdx.x; i < nwork;
+       i += (long)gridDim.x * KT_NTH) {
+    const long rowh = i / hv;                 // (b*Tq + t)*heads_total + h
+    const int c = (int)(i - rowh * hv);
+    const long tok = rowh / heads_total;      // b*Tq + t
+    const int h = (int)(rowh - tok * heads_total);
+    const int b = (int)(tok / Tq);
+    const int t = (int)(tok - (long)b * Tq);
+    const long p = (long)pos[b] + t;
+    const bool isq = h < Hq;
+    const bool isk = !isq && h < Hq + Hkv;
+    const int hh = isq ? 0 : (isk ? h - Hq : h - Hq - Hkv);
+    // liveness is a property of the token: uniform over the lanes of a row
+    const long dst =
+        KtPagedDest{page_table, NP, P, Hkv}.row(b, p, t < qlens[b], hh);
+    if (dst < 0) {
+      if (isq) {  // zero q row, pools untouched
+        bf16x8 z;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) z.h[j] = 0;
+        bf16x8* qd = q + (tok * Hq + h) * dv8;
+        qd[c] = z;
+        qd[c + hv] = z;
+      }
+      continue;
+    }
+    const bf16x8* src = qkv + rowh * dv8;
+    bf16x8 o1 = src[c];
+    bf16x8 o2 = src[c + hv];
+    if (isq || isk) {
+      const bf16x8 x1 = o1, x2 = o2;
+      const float* cosr = tab_cos + p * (hv * 8);
+      const float* sinr = tab_sin + p * (hv * 8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float cs = cosr[c * 8 + j];
+        const float sn = sinr[c * 8 + j];
+        const float a = bfbits2f(x1.h[j]);
+        const float bb = bfbits2f(x2.h[j]);
+        o1.h[j] = f2bfbits(a * cs - bb * sn);
+        o2.h[j] = f2bfbits(bb * cs + a * sn);
+      }
+    }
+    if (isq) {
+      bf16x8* qd = q + (tok * Hq + h) * dv8;
+      qd[c] = o1;
+      qd[c + hv] = o2;
+      continue;
+    }
+    // the bf16 row the bf16 kernels would have stored, quantized
+    float f1[8], f2[8];
+    f8_unpack_bf8(o1, f1);
+    f8_unpack_bf8(o2, f2);
+    const float amax = f8_group_max<HV>(fmaxf(f8_amax8(f1), f8_amax8(f2)));
+    float scale, inv;
+    f8_row_scale(amax, &scale, &inv);
+    uint2 c1 = f8_pack8(f1, inv), c2 = f8_pack8(f2, inv);
+    if (!(amax > 0.f)) c1 = c2 = make_uint2(0u, 0u);
+    uint2* pool = isk ? kpool : vpool;
+    pool[dst * dv8 + c] = c1;
+    pool[dst * dv8 + c + hv] = c2;
+    if (c == 0) (isk ? kscale : vscale)[dst] = scale;
+  }
+}
+
 template <int D, int R>
 void launch_fp8(const void* q, const void* k, const void* v,
                 const float* kscale, const float* vscale, const int* lens,
@@ -532,13 +636,6 @@ bool launch_fp8_r(int R, const void* q, const void* k, const void* v,
     default: return false;
   }
 #undef F8_CASE
-}
-
-int f8_grid(long nwork) {
-  long grid = (nwork + BLOCK_Q8 - 1) / BLOCK_Q8;
-  if (grid > 8192) grid = 8192;
-  if (grid < 1) grid = 1;
-  return (int)grid;
 }
 
 }  // namespace
@@ -575,16 +672,36 @@ hipError_t tok_kv_quantize_append(const void* k, const void* v, void* kcache,
                                   const int* pos, const int* qlens, int B,
                                   int Tq, int Tmax, int Hkv, int D,
                                   hipStream_t stream) {
-  const int lpr = D / 8;
-  const int grid = f8_grid((long)B * Tq * 2 * Hkv * lpr);
+  const int grid = kt_append_grid((long)B * Tq * 2 * Hkv * (D / 8));
   if (D == 128)
-    kv_quantize_append_kernel<16><<<grid, BLOCK_Q8, 0, stream>>>(
+    kv_quantize_append_kernel<16><<<grid, KT_NTH, 0, stream>>>(
         (const bf16x8*)k, (const bf16x8*)v, (uint2*)kcache, (uint2*)vcache,
         kscale, vscale, pos, qlens, B, Tq, Tmax, Hkv);
   else if (D == 64)
-    kv_quantize_append_kernel<8><<<grid, BLOCK_Q8, 0, stream>>>(
+    kv_quantize_append_kernel<8><<<grid, KT_NTH, 0, stream>>>(
         (const bf16x8*)k, (const bf16x8*)v, (uint2*)kcache, (uint2*)vcache,
         kscale, vscale, pos, qlens, B, Tq, Tmax, Hkv);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t tok_kv_quantize_append_paged(const void* k, const void* v,
+                                        void* kpool, void* vpool,
+                                        float* kscale, float* vscale,
+                                        const int* pos, const int* qlens,
+                                        const int* page_table, int B, int Tq,
+                                        int NP, int P, int Hkv, int D,
+                                        hipStream_t stream) {
+  const int grid = kt_append_grid((long)B * Tq * 2 * Hkv * (D / 8));
+  if (D == 128)
+    kv_quantize_append_paged_kernel<16><<<grid, KT_NTH, 0, stream>>>(
+        (const bf16x8*)k, (const bf16x8*)v, (uint2*)kpool, (uint2*)vpool,
+        kscale, vscale, pos, qlens, page_table, B, Tq, NP, P, Hkv);
+  else if (D == 64)
+    kv_quantize_append_paged_kernel<8><<<grid, KT_NTH, 0, stream>>>(
+        (const bf16x8*)k, (const bf16x8*)v, (uint2*)kpool, (uint2*)vpool,
+        kscale, vscale, pos, qlens, page_table, B, Tq, NP, P, Hkv);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
@@ -596,16 +713,38 @@ hipError_t tok_qkv_rope_append_fp8(const void* qkv, void* q, void* kcache,
                                    const int* pos, const int* qlens, int B,
                                    int Tq, int Tmax, int Hq, int Hkv, int D,
                                    hipStream_t stream) {
-  const int hv = (D / 2) / 8;
-  const int grid = f8_grid((long)B * Tq * (Hq + 2 * Hkv) * hv);
+  const int grid =
+      kt_append_grid((long)B * Tq * (Hq + 2 * Hkv) * ((D / 2) / 8));
   if (D == 128)
-    qkv_rope_append_fp8_kernel<8><<<grid, BLOCK_Q8, 0, stream>>>(
+    qkv_rope_append_fp8_kernel<8><<<grid, KT_NTH, 0, stream>>>(
         (const bf16x8*)qkv, (bf16x8*)q, (uint2*)kcache, (uint2*)vcache, kscale,
         vscale, cos_tab, sin_tab, pos, qlens, B, Tq, Tmax, Hq, Hkv);
   else if (D == 64)
-    qkv_rope_append_fp8_kernel<4><<<grid, BLOCK_Q8, 0, stream>>>(
+    qkv_rope_append_fp8_kernel<4><<<grid, KT_NTH, 0, stream>>>(
         (const bf16x8*)qkv, (bf16x8*)q, (uint2*)kcache, (uint2*)vcache, kscale,
         vscale, cos_tab, sin_tab, pos, qlens, B, Tq, Tmax, Hq, Hkv);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t tok_qkv_rope_append_paged_fp8(
+    const void* qkv, void* q, void* kpool, void* vpool, float* kscale,
+    float* vscale, const float* cos_tab, const float* sin_tab, const int* pos,
+    const int* qlens, const int* page_table, int B, int Tq, int NP, int P,
+    int Hq, int Hkv, int D, hipStream_t stream) {
+  const int grid =
+      kt_append_grid((long)B * Tq * (Hq + 2 * Hkv) * ((D / 2) / 8));
+  if (D == 128)
+    qkv_rope_append_paged_fp8_kernel<8><<<grid, KT_NTH, 0, stream>>>(
+        (const bf16x8*)qkv, (bf16x8*)q, (uint2*)kpool, (uint2*)vpool, kscale,
+        vscale, cos_tab, sin_tab, pos, qlens, page_table, B, Tq, NP, P, Hq,
+        Hkv);
+  else if (D == 64)
+    qkv_rope_append_paged_fp8_kernel<4><<<grid, KT_NTH, 0, stream>>>(
+        (const bf16x8*)qkv, (bf16x8*)q, (uint2*)kpool, (uint2*)vpool, kscale,
+        vscale, cos_tab, sin_tab, pos, qlens, page_table, B, Tq, NP, P, Hq,
+        Hkv);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
