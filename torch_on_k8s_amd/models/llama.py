@@ -435,6 +435,13 @@ class LlamaModel(nn.Module):
         tie_embeddings. None (the default) is the bf16 path. Combines with
         kv_dtype, prefill_chunk and the sampling arguments.
 
+        weight_dtype="mxfp4" is the same with OCP MXFP4 weights (e2m1 codes,
+        one e8m0 scale per 32 elements, 4.25 bits per weight) from
+        ops.quantize_weight_mxfp4 through ops.linear_w4: a decode step reads
+        a good quarter of the bf16 weight bytes. The hidden sizes must be
+        multiples of 32. It combines with everything "fp8" combines with; the
+        two modes share the cache of quantized copies.
+
         kv_page_size=64 keeps the KV cache in pages of 64 tokens instead of
         a [B, S0max + max_new_tokens] rectangle: per layer a pool
         [P, Hkv, 64, D] of exactly ops.kv_pages_needed(lens, max_new_tokens)
@@ -469,10 +476,11 @@ class LlamaModel(nn.Module):
                              "kv_dtype='fp8_paged')")
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1 or None")
-        if weight_dtype not in (None, "fp8"):
-            raise ValueError(f"weight_dtype must be None or 'fp8', got "
-                             f"{weight_dtype!r}")
-        w8 = weight_dtype == "fp8"
+        if weight_dtype not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"weight_dtype must be None, 'fp8' or 'mxfp4', "
+                             f"got {weight_dtype!r}")
+        wq = weight_dtype is not None        # quantized projections
+        qlinear = ops.linear_w4 if weight_dtype == "mxfp4" else ops.linear_w8
         fp8 = kv_dtype == "fp8"
         if fp8 and prefill_chunk is not None:
             raise ValueError("kv_dtype='fp8' has no chunked prefill: "
@@ -519,14 +527,14 @@ class LlamaModel(nn.Module):
             seed_t = torch.tensor(seeds, dtype=torch.long, device=dev)
 
         def lin(mod, x):
-            """A projection: the module's own call, or ops.linear_w8 over
-            its quantized weight."""
-            if not w8:
+            """A projection: the module's own call, or ops.linear_w8 /
+            ops.linear_w4 over its quantized weight."""
+            if not wq:
                 return mod(x)
-            return ops.linear_w8(x, *self._quantized(mod.weight))
+            return qlinear(x, *self._quantized(mod.weight, weight_dtype))
 
         def mlp(blk, x):
-            if not w8:
+            if not wq:
                 return blk.mlp(x)
             return lin(blk.mlp.down_proj,
                        ops.swiglu(lin(blk.mlp.gate_up_proj, x)))
@@ -596,7 +604,7 @@ class LlamaModel(nn.Module):
                 pg_i = page_table[bi, ti // PG].long()
             cs0, sn0 = cos[:S0].contiguous(), sin[:S0].contiguous()
             for i, blk in enumerate(self.layers):
-                if w8:
+                if wq:
                     q, k, v = ops.qkv_rope(
                         lin(blk.attn.qkv_proj, blk.input_norm(x)), cs0, sn0,
                         Hq, Hkv, D)
@@ -749,19 +757,22 @@ class LlamaModel(nn.Module):
                                                   device=dev)]))
         return out
 
-    def _quantized(self, weight: torch.Tensor):
-        """(codes, wscale) of a projection weight for weight_dtype="fp8",
-        built on first use and again after the weight changed."""
+    def _quantized(self, weight: torch.Tensor, mode: str = "fp8"):
+        """(codes, scales) of a projection weight for weight_dtype=mode,
+        built on first use and again after the weight changed. One cache for
+        both modes, keyed by (weight, mode)."""
         cache = self.__dict__.setdefault("_w8_cache", {})
-        key = weight.data_ptr()
+        key = (weight.data_ptr(), mode)
         ent = cache.get(key)
         if ent is None or ent[0] != weight._version:
-            ent = (weight._version, *ops.quantize_weight_fp8(weight))
+            quantize = (ops.quantize_weight_mxfp4 if mode == "mxfp4"
+                        else ops.quantize_weight_fp8)
+            ent = (weight._version, *quantize(weight))
             cache[key] = ent
         return ent[1], ent[2]
 
     def drop_quantized_weights(self) -> None:
-        """Free the e4m3 copies that weight_dtype="fp8" built."""
+        """Free the copies that weight_dtype="fp8" and "mxfp4" built."""
         self.__dict__.pop("_w8_cache", None)
 
     def num_params(self) -> int:

@@ -1229,6 +1229,119 @@ def linear_w8(x: torch.Tensor, codes: torch.Tensor, wscale: torch.Tensor, *,
 
 
 # --------------------------------------------------------------------------
+# MXFP4 weight-only linear: e2m1 codes [N,K/2] + one e8m0 byte per 32 elements
+# --------------------------------------------------------------------------
+_W4_TARGET_BLOCKS = 256    # about one block per CU (w8: two), by the sweep
+_W4_BLOCK_N = 64           # output channels per block of linear_w4_kernel
+_W4_STEP_K = 128           # k per step
+_W4_MIN_STEPS = 4          # K-steps per split, at least
+_W4_MAX_SPLITS = 16
+_W4_MAX_M = 64             # rows the kernel serves; above it: dequant + GEMM
+_W4_BLOCK = 32             # elements per scale
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def _e8m0(scales: torch.Tensor) -> torch.Tensor:
+    """2^(byte - 127) as fp32, the kernel's one shift (byte >= 2)."""
+    return (scales.to(torch.int32) << 23).view(torch.float32)
+
+
+def quantize_weight_mxfp4(w: torch.Tensor):
+    """A 2-D weight [N, K], K % 32 == 0, read as bf16, in OCP MXFP4:
+    (codes uint8 [N, K/2], scales uint8 [N, K/32]). Element k sits in byte
+    k // 2, even k in the low nibble; a nibble is sign bit | e2m1 code
+    (magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6). A block of 32 has the e8m0 scale
+    byte clamp(floor(log2(amax)) - 2 + 127, 2, 254); an element is
+    v / 2^(byte - 127), saturated to +-6 and rounded to the nearest grid
+    point, ties to the even code. The lower clamp is 2, not 0: 0.5 * 2^(2-127)
+    is the smallest normal bf16, so every dequantized value is exactly a bf16
+    value and the kernel's widening is exact. Plain torch, runs once."""
+    if w.dim() != 2 or w.shape[1] % _W4_BLOCK != 0:
+        raise ValueError(f"mxfp4 takes a 2-D weight [N, K] with K a multiple "
+                         f"of {_W4_BLOCK}, got {tuple(w.shape)}")
+    N, K = w.shape
+    v = w.detach().to(torch.bfloat16).float().view(N, K // _W4_BLOCK, _W4_BLOCK)
+    exp = torch.frexp(v.abs().amax(-1))[1] - 1          # floor(log2(amax))
+    scales = (exp - 2 + 127).clamp(2, 254).to(torch.uint8)
+    a = (v / _e8m0(scales)[..., None]).abs()
+    # midpoints of the grid; >= where the tie goes up to the even code
+    code = ((a > 0.25).int() + (a >= 0.75) + (a > 1.25) + (a >= 1.75)
+            + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+    nib = (code + 8 * ((v < 0) & (code > 0))).to(torch.uint8).view(N, K)
+    return nib[:, 0::2] | (nib[:, 1::2] << 4), scales
+
+
+def dequant_mxfp4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """The fp32 [N, K] values of MXFP4 codes [N, K/2] and scales [N, K/32]
+    (each exactly a bf16 value for scale bytes >= 2)."""
+    grid = torch.tensor(_E2M1 + tuple(-g for g in _E2M1), device=codes.device)
+    nib = torch.stack((codes & 15, codes >> 4), -1).view(codes.shape[0], -1)
+    return grid[nib.long()] * _e8m0(scales).repeat_interleave(_W4_BLOCK, 1)
+
+
+def linear_w4_splits(M: int, N: int, K: int) -> int:
+    """Default K-split count of linear_w4: linear_w8_splits' rule (the step
+    is 128 k in both kernels) aiming at one block per CU instead of two. The
+    sweep over 1..16 splits on the llama-1b shapes at M = 8
+    (profiles/linear_w4.log) has its best time there on four projections and
+    is 4% off it on down_proj; two per CU costs gate_up_proj a quarter and
+    down_proj a fifth. Depends on shapes
+    alone, so a captured grid stays valid."""
+    blocks = -(-N // _W4_BLOCK_N)
+    want = _W4_TARGET_BLOCKS // max(1, blocks)
+    return max(1, min(want, (K // _W4_STEP_K) // _W4_MIN_STEPS,
+                      _W4_MAX_SPLITS))
+
+
+def _check_w4(x, codes, scales):
+    if codes.dtype != torch.uint8 or codes.dim() != 2:
+        raise ValueError("codes must be uint8 [N,K/2]")
+    if scales.dtype != torch.uint8 or tuple(scales.shape) != (
+            codes.shape[0], codes.shape[1] // 16):
+        raise ValueError("scales must be uint8 [N,K/32]")
+    if x is not None and x.shape[-1] != 2 * codes.shape[1]:
+        raise ValueError(f"x has {x.shape[-1]} features, codes have "
+                         f"K = {2 * codes.shape[1]}")
+
+
+@torch.no_grad()
+def w4_dequant(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """MXFP4 codes and scales (ops.quantize_weight_mxfp4) as a [N, K] bf16
+    weight; exact."""
+    _check_w4(None, codes, scales)
+    if codes.is_cuda:
+        return _require_ext("w4_dequant").w4_dequant(codes, scales)
+    return dequant_mxfp4(codes, scales).to(torch.bfloat16)
+
+
+@torch.no_grad()
+def linear_w4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, *,
+              num_splits: int | None = None) -> torch.Tensor:
+    """y = x @ dequant(codes, scales)^T over the last dimension of x. codes:
+    [N, K/2] uint8, scales: [N, K/32] uint8 (ops.quantize_weight_mxfp4). On
+    the GPU x is bf16, K % 128 == 0 and N % 16 == 0; up to 64 rows run
+    linear_w4_kernel (the codes are widened in registers with the block scale
+    folded in and fed to bf16 MFMAs, no rounding before the fp32
+    accumulator), more rows dequantize to a bf16 temporary and make the
+    library call of the bf16 path. No autograd: a serving op."""
+    _check_w4(x, codes, scales)
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    if not x.is_cuda:
+        return torch.nn.functional.linear(
+            x.float(), dequant_mxfp4(codes, scales)).to(x.dtype)
+    x2 = x.reshape(-1, K).contiguous()
+    M = x2.shape[0]
+    ext = _require_ext("linear_w4")
+    if M <= _W4_MAX_M:
+        if num_splits is None:
+            num_splits = linear_w4_splits(M, N, K)
+        y = ext.linear_w4(x2, codes, scales, int(num_splits))
+    else:
+        y = torch.nn.functional.linear(x2, ext.w4_dequant(codes, scales))
+    return y.view(*x.shape[:-1], N)
+
+
+# --------------------------------------------------------------------------
 # Token sampling: temperature / top-k / top-p, one draw per row (no autograd)
 # --------------------------------------------------------------------------
 _PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
@@ -1785,4 +1898,6 @@ __all__ = [
     "qkv_rope_append_paged_fp8_", "kv_quantize_append_paged_",
     "sample_tokens", "sample_uniform", "philox4x32_10",
     "linear_w8", "linear_w8_splits", "quantize_weight_fp8", "w8_dequant",
+    "linear_w4", "linear_w4_splits", "quantize_weight_mxfp4", "w4_dequant",
+    "dequant_mxfp4",
 ]

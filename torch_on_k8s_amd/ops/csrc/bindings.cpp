@@ -157,6 +157,11 @@ hipError_t tok_linear_w8(const void* x, const void* code, const float* wscale,
                          int num_splits, hipStream_t stream);
 hipError_t tok_w8_dequant(const void* code, const float* wscale, void* out,
                           long N, int K, hipStream_t stream);
+hipError_t tok_linear_w4(const void* x, const void* code, const void* scale,
+                         void* y, float* ws, int M, int N, int K,
+                         int num_splits, hipStream_t stream);
+hipError_t tok_w4_dequant(const void* code, const void* scale, void* out,
+                          long N, int K, hipStream_t stream);
 int tok_sample_max_vocab();
 hipError_t tok_sample_tokens(const void* logits, long row_stride,
                              const float* temperature, const int* top_k,
@@ -1182,6 +1187,61 @@ at::Tensor w8_dequant(at::Tensor codes, at::Tensor wscale) {
   return out;
 }
 
+// MXFP4 weight: e2m1 codes [N,K/2] (two per byte) in the nn.Linear layout and
+// one e8m0 scale byte per 32 elements [N,K/32]. Returns K.
+long check_w4_weight(const at::Tensor& codes, const at::Tensor& scales) {
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte &&
+                  codes.is_contiguous() && codes.dim() == 2,
+              "codes must be a contiguous uint8 GPU tensor [N,K/2]");
+  const long N = codes.size(0), K = 2 * codes.size(1);
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && K < (1L << 22),
+              "linear_w4: K must be a multiple of 128 (below 2^22), got ", K);
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && N <= 64L * 65535,
+              "linear_w4: N must be a multiple of 16, got ", N);
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == at::kByte &&
+                  scales.is_contiguous() && scales.dim() == 2 &&
+                  scales.size(0) == N && scales.size(1) == K / 32,
+              "scales must be a contiguous uint8 GPU tensor [N,K/32]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0,
+              "linear_w4: codes must be 16-byte aligned");
+  return K;
+}
+
+// y[M,N] = x[M,K] . dequant(codes, scales)^T for 1 <= M <= 64.
+at::Tensor linear_w4(at::Tensor x, at::Tensor codes, at::Tensor scales,
+                     long num_splits) {
+  CHECK_BF16_CUDA(x);
+  const long K = check_w4_weight(codes, scales), N = codes.size(0);
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == K, "x must be [M,K], K = ", K);
+  const long M = x.size(0);
+  TORCH_CHECK(M >= 1 && M <= 64,
+              "linear_w4: the kernel serves 1 <= M <= 64 rows, got ", M);
+  TORCH_CHECK(num_splits >= 1 && num_splits <= 1024,
+              "linear_w4: num_splits out of range");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "linear_w4: x must be 16-byte aligned");
+  auto y = at::empty({M, N}, x.options());
+  at::Tensor ws;
+  float* wsp = nullptr;
+  if (num_splits > 1) {
+    ws = at::empty({num_splits * M * N}, x.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  TOK_HIP_OK(tok_linear_w4(x.data_ptr(), codes.data_ptr(), scales.data_ptr(),
+                           y.data_ptr(), wsp, (int)M, (int)N, (int)K,
+                           (int)num_splits, current_stream()));
+  return y;
+}
+
+// The exact bf16 value of every code as a [N,K] bf16 weight.
+at::Tensor w4_dequant(at::Tensor codes, at::Tensor scales) {
+  const long K = check_w4_weight(codes, scales), N = codes.size(0);
+  auto out = at::empty({N, K}, codes.options().dtype(at::kBFloat16));
+  TOK_HIP_OK(tok_w4_dequant(codes.data_ptr(), scales.data_ptr(),
+                            out.data_ptr(), N, (int)K, current_stream()));
+  return out;
+}
+
 // logits: [B, V] bf16, unit stride in V, any row stride. The per-row
 // parameters are [B] device tensors that the host never reads; u replaces
 // the generator's draw when given. Returns int64 [B].
@@ -1512,6 +1572,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("num_splits"));
   mod.def("w8_dequant", &w8_dequant,
           "e4m3 weight codes * per-channel scale -> bf16 weight (gfx950)");
+  mod.def("linear_w4", &linear_w4,
+          "Skinny-M linear over MXFP4 weights, e2m1 codes with e8m0 block "
+          "scales (gfx950)",
+          py::arg("x"), py::arg("codes"), py::arg("scales"),
+          py::arg("num_splits"));
+  mod.def("w4_dequant", &w4_dequant,
+          "MXFP4 weight codes and block scales -> bf16 weight (gfx950)");
   mod.def("sample_tokens", &sample_tokens,
           "Fused temperature / top-k / top-p sampler (bf16, gfx950)",
           py::arg("logits"), py::arg("temperature"), py::arg("top_k"),

@@ -379,6 +379,16 @@ void launch_w8(const void* x, const void* code, const float* wscale, void* y,
 
 extern "C" {
 
+// linear_w8_combine_kernel over nvec 4-float groups: y = bf16(the sum of the
+// num_splits fp32 partial images in ws, in split order). linear_w4.hip folds
+// its splits through it as well.
+hipError_t tok_split_combine(const float* ws, void* y, long nvec,
+                             int num_splits, hipStream_t stream) {
+  linear_w8_combine_kernel<<<w8_grid(nvec), W8_NTH, 0, stream>>>(
+      (const f32x4v*)ws, (uint2*)y, nvec, num_splits);
+  return hipGetLastError();
+}
+
 // ws: fp32, num_splits*M*N elements; unused when num_splits == 1.
 hipError_t tok_linear_w8(const void* x, const void* code, const float* wscale,
                          void* y, float* ws, int M, int N, int K,
@@ -394,12 +404,8 @@ hipError_t tok_linear_w8(const void* x, const void* code, const float* wscale,
     default: launch_w8<4>(x, code, wscale, y, ws, M, N, K, num_splits, stream); break;
   }
   HIP_CHECK(hipGetLastError());
-  if (num_splits > 1) {
-    const long nvec = (long)M * N / 4;
-    linear_w8_combine_kernel<<<w8_grid(nvec), W8_NTH, 0, stream>>>(
-        (const f32x4v*)ws, (uint2*)y, nvec, num_splits);
-    HIP_CHECK(hipGetLastError());
-  }
+  if (num_splits > 1)
+    HIP_CHECK(tok_split_combine(ws, y, (long)M * N / 4, num_splits, stream));
   return hipSuccess;
 }
 

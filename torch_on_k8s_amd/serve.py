@@ -35,8 +35,9 @@ Endpoints:
                                   "kv_page_size": 64 keeps the KV cache in
                                   64-token pages (ragged only);
                                   "weight_dtype": "fp8" runs the projections
-                                  on e4m3 weights with per-channel scales
-                                  (ragged only)
+                                  on e4m3 weights with per-channel scales,
+                                  "weight_dtype": "mxfp4" on MXFP4 weights
+                                  (e2m1, one scale per 32) (ragged only)
 
 Prompts are token IDs: this framework is tokenizer-free by design
 (synthetic-data training; no network for vocab downloads).
@@ -159,7 +160,8 @@ class InferenceServer:
         response carries it: row b draws with seed + b. prefill_chunk, when
         given, prefills through the cache in chunks of that many tokens;
         kv_dtype="fp8" keeps the KV cache in e4m3 with per-row scales;
-        weight_dtype="fp8" runs the projections on e4m3 weights;
+        weight_dtype="fp8" runs the projections on e4m3 weights,
+        weight_dtype="mxfp4" on MXFP4 weights;
         kv_page_size=64 keeps the KV cache in 64-token pages."""
         import torch
         sampled = temperature > 0
@@ -258,8 +260,9 @@ def build_app(srv: InferenceServer):
         if req.kv_dtype not in (None, "fp8", "fp8_paged"):
             raise HTTPException(400, 'kv_dtype must be "fp8", "fp8_paged" '
                                      'or absent')
-        if req.weight_dtype not in (None, "fp8"):
-            raise HTTPException(400, 'weight_dtype must be "fp8" or absent')
+        if req.weight_dtype not in (None, "fp8", "mxfp4"):
+            raise HTTPException(400, 'weight_dtype must be "fp8", "mxfp4" '
+                                     'or absent')
         if req.kv_page_size not in (None, 64):
             raise HTTPException(400, "kv_page_size must be 64 or absent")
         if req.kv_page_size is not None and req.kv_dtype == "fp8":
